@@ -1,18 +1,22 @@
 """Headline benchmark: train images/s of the Pix2Pix GAN step (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, ramps the clocks, runs the W warm-up steps, times the K steps, writes what the last of them
+computed when --dump-outputs is given, and prints the line.  --full adds the figures that take runs of their own:
+the host cost of issuing a step, the per-kernel rooflines and the CPU baseline.
 
 One "step" = UnetWrapper.training_step on one synthetic batch already resident in HBM:
 D phase + G phase, both Adam updates and the per-step SSIM/PSNR/RMSE (reference
 models/wrapper.py:117-162), 256x256x1 pairs, 64 images per GPU (weak scaling), bf16 storage /
 fp32 accumulate.  Rank 0 prints ONE JSON line.
 
-roofline: every convolution launch is timed with HIP events recorded on the stream it is launched
+roofline (--full): every convolution launch is timed with HIP events recorded on the stream it is launched
 on and keyed by the kernel symbol rocprofv3 reports (pai_conv_kernel_name); the kernel with the
 largest summed time is the dominant one: achieved = algorithmic FLOPs of its launches / their
 summed duration, against the dense bf16 MFMA peak.
-cpu_baseline: the oracle's CPU restatement of the same step (same ATen ops the reference
+cpu_baseline (--full): the oracle's CPU restatement of the same step (same ATen ops the reference
 dispatches to), timed on this box's host cores on a bounded sample (rank 0, N=1 only).
 """
 import argparse
@@ -30,8 +34,13 @@ sys.path.insert(0, ROOT)
 MULTS = (1, 2, 4, 8, 8, 8, 8, 8)
 TRANS_MULTS = (1, 2, 2, 4, 4)       # TransUnetGAN's class default; the CLI default of 8 levels leaves no patches
 SIZE = 256
-PEAK_BF16_TFLOPS = 2500.0      # dense bf16 MFMA, /opt/skills/guides/MI355X_MICROARCH.md
-PEAK_HBM_GBS = 8000.0          # HBM3E, same guide
+PEAK_BF16_TFLOPS = 2500.0      # dense bf16 MFMA, MI355X
+PEAK_HBM_GBS = 8000.0          # HBM3E, MI355X
+# Untimed steps before the W warm-up ones: an idle box starts in a low-power state and needs ~2 s of load to reach its
+# sustained clocks (the first 25 steps measured 20-25 % slower than the next 25).  A fixed count, not "until the step
+# time settles": every step trains, and what --dump-outputs writes repeats from run to run only if the number of steps
+# before it does.  400 steps of the headline workload are ~2.4 s, more than the settling rule took on most runs.
+CLOCK_RAMP_STEPS = 400
 # conv MACs per image: generator G, discriminator D, first layers G1, D1
 G_MAC, D_MAC, G1_MAC, D1_MAC = 5_947_523_072, 1_646_010_368, 16_777_216, 33_554_432
 
@@ -113,6 +122,63 @@ def cpu_baseline(attention=False, b4=(3, 20), b64=(3, 5)):
             "value_b64": None if v64 is None else round(v64, 3)}
 
 
+def dump_outputs(model, out_dir, max_values=1 << 22, per_tensor=1 << 16):
+    """What the last step handed its caller, as DIR/<name>.npy: each logged scalar (d_loss, loss, train_ssim,
+    train_psnr, train_rmse) in float64, and the generator's and the discriminator's state after the step's optimizer
+    updates (parameters and BatchNorm buffers in state-dict order) as one float64 vector each.  A tensor of more than
+    `per_tensor` elements contributes a fixed, seeded sample of them; at most `max_values` values in all (32 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in sorted(model.logged.items()):
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.array(float(v), dtype=np.float64))
+    states = {"generator": model.unet.state_dict(), "discriminator": model.discriminator.state_dict()}
+    per = min(per_tensor, max_values // sum(len(sd) for sd in states.values()))
+    rng = np.random.default_rng(0)
+    for name, sd in states.items():
+        parts = []
+        for v in sd.values():
+            flat = v.detach().reshape(-1)
+            if flat.numel() > per:
+                idx = np.sort(rng.integers(0, flat.numel(), per))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            parts.append(flat.double().cpu())
+        np.save(os.path.join(out_dir, f"{name}.npy"), torch.cat(parts).numpy())
+
+
+class TrainingState:
+    """A copy of the floating-point training state -- parameters, BatchNorm buffers, Adam moments -- written back in
+    place (a recorded launch plan holds the addresses) before the last timed step when --dump-outputs is given.  The
+    GAN step is not bit-reproducible from run to run, and hundreds of training steps turn last-bit differences into
+    percent-level ones (7 % in d_loss after 600 steps, measured); from a restored state the dumped step starts where it
+    started on every other run.  The optimizers' step counts are not touched: the number of steps is fixed."""
+
+    def __init__(self, model):
+        self.model = model
+        self.live = [v for v in model.state_dict().values() if v.is_floating_point()]
+        for opt in model._all_optimizers():
+            arena = opt._engine.arena() if hasattr(opt, "_engine") else None
+            if getattr(arena, "mflat", None) is not None:
+                self.live += [arena.mflat, arena.vflat]
+            else:
+                self.live += [st[k] for st in opt.state.values() for k in ("exp_avg", "exp_avg_sq") if k in st]
+        self.saved = [v.detach().clone() for v in self.live]
+
+    def restore(self):
+        from thesis_pai_reconstruction_amd import ops
+        with torch.no_grad():
+            for v, s in zip(self.live, self.saved):
+                v.copy_(s)
+        # the bf16 filter packs follow the master weights: rewrite the current ones from the restored weights
+        for mod in self.model.modules():
+            eng = getattr(mod, "engine", None) if hasattr(type(mod), "engine") else None
+            for pk in (eng.all_packs() if eng is not None else ()):
+                if pk.dtype is None or pk.wf is None:
+                    continue
+                w, cout, taps, cin, wf_out, wd_out = pk._prepare(pk.dtype)
+                if wf_out is not None or wd_out is not None:
+                    ops.pack_weights(pk.dtype, w, cout, taps, cin, wf_out, wd_out)
+                pk._mark(pk.dtype)
+
+
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: start N worker processes (one rank each, torchrun-style
     environment, rendezvous on 127.0.0.1) and wait for them.  This parent never touches the GPU -- it runs before
@@ -177,9 +243,16 @@ def main():
     ap.add_argument("--rccl-proto", default=None, choices=["Simple", "LL", "LL128"], help="force NCCL_PROTO")
     ap.add_argument("--rccl-channels", type=int, default=None, help="force NCCL_MIN_NCHANNELS = NCCL_MAX_NCHANNELS")
     ap.add_argument("--precision", default="bf16-mixed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: host issue time per step, the per-kernel "
+                         "rooflines (an eager repeat of the K steps with HIP events per launch, 3 more steps without the "
+                         "weight-gradient overlap) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (logged losses and metrics, a seeded "
+                         "sample of the updated generator and discriminator state) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="do not bracket the convolution launches with HIP events in the timed region (no roofline)")
+                    help="--full without the per-launch HIP events of the roofline repeat (no roofline)")
     ap.add_argument("--no-reuse", action="store_true", help="literal two generator forwards per step")
     ap.add_argument("--model", default="pix2pix", choices=["pix2pix", "attention_unet", "resnext_unet", "trans_unet"],
                     help="pix2pix = BASELINE configs[1] (the headline metric); attention_unet = configs[2]; "
@@ -193,6 +266,8 @@ def main():
                     help="name=value,... launch-configuration switches (pai_set_tunable) for A/B runs on one box; the "
                          "line then carries them under config.tunables")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))        # before anything touches the GPU
 
@@ -265,53 +340,64 @@ def main():
         else:
             model.training_step(b, i)
 
-    # Clock ramp: a box that has been idle starts in a low-power state and takes a few seconds of load
-    # to reach its sustained clocks (first 25 steps measured 20-25 % slower than the next 25).  Untimed
-    # groups of 10 steps run until two consecutive groups agree within 2 % (at least 2 s, at most 20 s);
-    # all ranks take the same decision.  These come BEFORE the W warm-up steps and the K timed ones.
-    prewarm_steps, prev, t_start = 0, None, time.perf_counter()
-    while True:
-        torch.cuda.synchronize()
+    # The clock ramp runs on a GPU of its own only: ranks that share one (over gloo) time the host all-reduce, not the chip.
+    prewarm_steps = CLOCK_RAMP_STEPS if world <= torch.cuda.device_count() else 0
+    state = None
+    for g in range(0, prewarm_steps, 10):
         tg = time.perf_counter()
         for i in range(10):
             run_step(batch, i)
         torch.cuda.synchronize()
-        cur = time.perf_counter() - tg
-        prewarm_steps += 10
-        elapsed = time.perf_counter() - t_start
-        stable = prev is not None and abs(cur - prev) <= 0.02 * prev and elapsed >= 2.0
+        if args.dump_outputs and state is None:
+            state = TrainingState(model)        # after the plan's eager warm-up and its recording: arenas in place
         if os.environ.get("PAI_BENCH_DEBUG"):
-            print(f"[clock ramp] t={elapsed:.2f}s {cur * 100:.3f} ms/step", file=sys.stderr, flush=True)
-        prev = cur
-        flag = torch.tensor([0.0 if (stable or elapsed >= 20.0) else 1.0], device=dev)
-        if world > 1:
-            torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MAX)
-        if float(flag) == 0.0:
-            break
+            print(f"[clock ramp] steps {g}-{g + 9}: {(time.perf_counter() - tg) * 100:.3f} ms/step", file=sys.stderr, flush=True)
     for i in range(args.warmup):
         run_step(batch, i)
     torch.cuda.synchronize()
-    # host-side cost of issuing one step (launches + autograd plumbing, or one graph launch), measured without
-    # waiting for the GPU: if this approaches ms_per_step the run is launch-bound, not kernel-bound
-    tq = time.perf_counter()
-    for i in range(3):
-        run_step(batch, i)
-    host_issue_ms = (time.perf_counter() - tq) / 3 * 1e3
-    torch.cuda.synchronize()
+    if args.dump_outputs and state is None:
+        state = TrainingState(model)
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(args.steps):
+    for i in range(args.steps - (state is not None)):
         run_step(batch, i)
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
+    if state is not None:                       # the last timed step, from the restored state (the copy is not timed)
+        state.restore()
+        torch.cuda.synchronize()
+        barrier()
+        t1 = time.perf_counter()
+        run_step(batch, args.steps - 1)
+        torch.cuda.synchronize()
+        barrier()
+        dt += time.perf_counter() - t1
+    if world > 1:
+        tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
+        torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
+        dt = float(tmax)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
+
+    # ---- --full: what the headline figure does not need ------------------------------------------------
+    # host-side cost of issuing one step (launches + autograd plumbing, or one graph launch), measured without
+    # waiting for the GPU: if this approaches ms_per_step the run is launch-bound, not kernel-bound
+    host_issue_ms = None
+    if args.full:
+        tq = time.perf_counter()
+        for i in range(3):
+            run_step(batch, i)
+        host_issue_ms = (time.perf_counter() - tq) / 3 * 1e3
+        torch.cuda.synchronize()
+        barrier()
     # Per-launch HIP events (two per convolution launch, on the launching stream) for the roofline are
     # taken over a REPEAT of the same K steps, not inside the timed ones: ~150 event records per step
     # put a barrier packet between back-to-back kernels and cost 2-5 ms/step (11.7-15.1 vs 9.9 ms
     # measured), which would make `value` a measurement of the instrumentation.
     prof, prof_hbm = [], []
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         ops.PROFILE, ops.PROFILE_HBM = [], []
         for i in range(args.steps):
             model.training_step(batch, i)
@@ -319,10 +405,6 @@ def main():
         prof, ops.PROFILE = ops.PROFILE, None
         prof_hbm, ops.PROFILE_HBM = ops.PROFILE_HBM, None
         barrier()
-    if world > 1:
-        tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
-        torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
-        dt = float(tmax)
 
     # ---- per-kernel roofline from the launches' own HIP events --------------------------------------
     def roofline_of(prof, nsteps, dom=None):
@@ -390,7 +472,7 @@ def main():
     # launches are timed once more with that overlap switched off (3 extra steps, not part of `value`).
     roofline_isolated = None
     engines = [m.engine for m in (model.unet, model.discriminator) if hasattr(type(m), "engine")]
-    if any(e._side.on for e in engines) and not args.no_kernel_events:
+    if args.full and any(e._side.on for e in engines) and not args.no_kernel_events:
         saved = [e._side.on for e in engines]
         for e in engines:
             e._side.on = False
@@ -439,7 +521,7 @@ def main():
                    **({"backend": torch.distributed.get_backend(), "gpus_visible": torch.cuda.device_count(),
                        "rccl_ranks": reducer.rccl_ranks() if reducer is not None else 0,
                        "gradient_exchange": reducer.describe() if reducer is not None else None} if world > 1 else {})},
-        "host_issue_ms_per_step": round(host_issue_ms, 3),
+        "host_issue_ms_per_step": None if host_issue_ms is None else round(host_issue_ms, 3),
         "launch_mode": ("launch plan (pai_plan_run: one C call per step)" if planned is not None and planned.replays > 0 else
                         "eager" + (f" (plan refused: {planned.disabled})" if planned is not None and planned.disabled else "")),
         "launch_plan": planned.describe() if planned is not None else None,
@@ -451,7 +533,7 @@ def main():
         "roofline_isolated": roofline_isolated,
         "roofline_hbm": roofline_hbm,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(attention=args.model == "attention_unet") if args.model not in ("resnext_unet", "trans_unet") else None
     else:
         out["cpu_baseline"] = None

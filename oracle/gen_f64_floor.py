@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 import oracle
+from oracle import golden
 from oracle.fingerprint import fingerprint, fingerprint_close
 from oracle.gen_golden import synth_batch
 
@@ -23,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def main(name):
-    z = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
+    z = golden.load(os.path.join(ROOT, "tests", "golden"), name)
     seed, n, size = int(z["meta.seed"]), int(z["meta.n"]), int(z["meta.size"])
     mults = tuple(int(v) for v in z["meta.mults"])
     fam = str(z["meta.family"]) if "meta.family" in z.files else "pix2pix"

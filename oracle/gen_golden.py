@@ -25,6 +25,8 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from oracle import golden
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 REF = "/root/reference"
@@ -172,7 +174,7 @@ def run_case(name, mults, size, n, loss_type, seed, steps, full_tensors, search=
         for k, v in m.unet.state_dict().items():
             if "running" in k or "num_batches" in k:
                 rec[f"final.gstate_full.{k}"] = v.numpy()
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **rec)
+    golden.save(OUT, name, rec)
     print("wrote", name, {k: float(v) for k, v in rec.items() if ".log." in k})
 
 
@@ -237,7 +239,7 @@ def run_trained_case(name, mults, size, n, seed, steps, family):
     rec["val.rmse_per_image"] = (pred_eval - t).pow(2).mean((1, 2, 3)).sqrt().numpy().astype(np.float64)
     for k, v in m.unet.state_dict().items():
         rec[f"final.gstate.{k}"] = fingerprint(v)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **rec)
+    golden.save(OUT, name, rec)
     print("wrote", name, {k: float(v) for k, v in rec.items() if k.startswith("val.log.")})
 
 
@@ -273,7 +275,7 @@ def run_forward_case(name, mults, size, n, seed, family="pix2pix"):
     rec["pred_full"] = pred.numpy()
     rec["logits_fake_full"] = logits_fake.numpy()
     rec["logits_real_full"] = logits_real.numpy()
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **rec)
+    golden.save(OUT, name, rec)
     print("wrote", name)
 
 

@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/.."
 for i in 1 2; do
   if [ -z "$AB_NO_BASE" ]; then
-    PAI_HIP_LIB=$PWD/thesis-pai-reconstruction_amd/libpai_hip_base.so timeout 300 python bench.py --no-cpu-baseline "$@" | python scripts/bench_line.py base
+    PAI_HIP_LIB=$PWD/thesis-pai-reconstruction_amd/libpai_hip_base.so timeout 300 python bench.py --full --no-cpu-baseline "$@" | python scripts/bench_line.py base
   fi
-  timeout 300 python bench.py --no-cpu-baseline "$@" | python scripts/bench_line.py new
+  timeout 300 python bench.py --full --no-cpu-baseline "$@" | python scripts/bench_line.py new
 done

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import oracle
+from oracle import golden
 from oracle.fingerprint import fingerprint, fingerprint_close
 from oracle.gen_golden import synth_batch
 
@@ -16,7 +17,7 @@ DEV = "cuda:0"
 
 
 def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name + ".npz"))
+    return golden.load(golden_dir, name)
 
 
 def build(pai, res_type, mults, loss_type, seed, dtype=torch.float32, dropout=0.0):

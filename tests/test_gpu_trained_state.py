@@ -23,6 +23,7 @@ import pytest
 import torch
 
 import oracle
+from oracle import golden
 from oracle.gen_golden import blob_batch
 from oracle.metrics_ref import ssim_full
 
@@ -34,7 +35,7 @@ def _load(golden_dir, name):
     path = os.path.join(golden_dir, name + ".npz")
     if not os.path.exists(path):
         pytest.skip(f"{name}.npz not generated (python -m oracle.gen_golden --trained)")
-    return np.load(path)
+    return golden.load(golden_dir, name)
 
 
 def _build(pai, family, mults, seed):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import oracle
+from oracle import golden
 from oracle.fingerprint import fingerprint, fingerprint_close
 from oracle.gen_golden import synth_batch
 from oracle.gen_ssim_skimage import pairs  # numpy only at import? (skimage imported lazily below)
@@ -17,7 +18,7 @@ RTOL = 2e-5   # same torch, same CPU ops: only thread-count reduction-order nois
 
 
 def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name + ".npz"))
+    return golden.load(golden_dir, name)
 
 
 def _states(meta_mults, seed, gan=True, family="pix2pix"):
