@@ -37,6 +37,7 @@ extern "C" {
 
 #define PAI_F32 0
 #define PAI_BF16 1
+#define PAI_U8 2          /* uint8 image bytes: the device-resident data set only (pai_batch_gather) */
 
 #define PAI_ACT_NONE 0
 #define PAI_ACT_LRELU 1   /* LeakyReLU(0.2)  models/pix2pix.py:62, models/wrapper.py:205 */
@@ -55,7 +56,8 @@ const char* pai_last_error(void);
  * experiment kernels: pack_flags MUST be zero); pai_conv_desc.reserved became .hints (PAI_HINT_SOLO).
  * 131: pai_lerp_multi (the EMA update of callbacks/ema.py), PAI_TUNE_<name> environment defaults of the tunables.
  * 132: input prologue (pai_conv_prologue_ok, pai_conv_fwd_pro, pai_conv_wgrad_pro); pai_instnorm_fwd / _bwd; pai_bn2_bwd_reduce / _apply; pai_bn_stats_buffer_rows grows for
- * layers with more than 2048 partial rows (callers that size the buffer through it need no change). */
+ * layers with more than 2048 partial rows (callers that size the buffer through it need no change).
+ * 133: device-resident data set (pai_resize_aa_u8, pai_batch_gather, pai_data_kernel_name), PAI_U8. */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -673,6 +675,28 @@ int pai_swap_mid(int elem_bytes, const void* src, int64_t A, int B, int C, int64
 /* ptr[0 .. numel) *= factor (fp32, 16-byte aligned): the x 1/world_size average behind the SUM all-reduce of a gradient
  * bucket (DDP averages, reference main.py:123-136 through pl.Trainer), as a node of the plan. */
 int pai_scale(float* ptr, int64_t numel, float factor, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Device-resident data set (reference dataset.py:51-59,77-107,129-132: decode, resize, scale and stack a batch -- there
+ * on the host, for every image of every epoch; here each file is decoded once and everything after it runs on the GPU).
+ *
+ * pai_resize_aa_u8: dst uint8 [n][S][S] = uint8(round_half_even(antialiased_bilinear(float(src uint8 [n][H][W])))),
+ * byte for byte what torch's interpolate(mode="bilinear", antialias=True, align_corners=False) + round + uint8 cast gives
+ * on the host.  The filter is separable (width first, fp32 in between); per axis the caller passes the tables of
+ * dataset.aa_tables(in, S) in device memory: bounds int32 [S][2] = (first source index, taps), weights fp32 [S][K],
+ * zero padded.  An axis whose size already is S takes NULL tables and is copied.  hbounds_host is the height bounds
+ * table in HOST memory (the launch geometry -- how many source rows a tile of output rows stages in LDS -- follows from
+ * it).  One output row may read at most 160 KB / (4 S) source rows.
+ * pai_batch_gather: out_a[b] = value(cache_a[indices[b]]), out_b[b] = value(cache_b[indices[b]]) for b < count, fp32
+ * [count][per_image].  src_dtype PAI_U8: value = table[byte] (256 fp32 entries on the device: byte / 255, or
+ * byte / 255 * 2 - 1, built by the caller), per_image a multiple of 16.  PAI_F32: a copy, per_image a multiple of 4, table
+ * unused.  indices: int64 on the device, each in [0, M) (others leave their output image unwritten).  16-byte aligned buffers.
+ * pai_data_kernel_name: symbol of the kernel behind op 0 (resize) / 1 (gather of src_dtype), as pai_conv_kernel_name. */
+int pai_resize_aa_u8(const void* src, int n, int H, int W, int S, const int* wbounds, const float* wweights, int KW,
+                     const int* hbounds, const float* hweights, int KH, const int* hbounds_host, void* dst, void* stream);
+int pai_batch_gather(int src_dtype, const void* cache_a, const void* cache_b, int64_t M, int64_t per_image,
+                     const int64_t* indices, int count, const float* table, float* out_a, float* out_b, void* stream);
+int pai_data_kernel_name(int op, int src_dtype, char* name, int name_len);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,8 @@
 (logs/<name>/version_k/{metrics.csv,checkpoints/best.ckpt}), running on the MI355X hot path.
 
 Added (build-only) flags: --synthetic N (train on N synthetic pairs instead of a YAML list),
---image-size, --num-workers.  Multi-GPU: launch with
+--image-size, --num-workers, --device-cache (decode every file once, keep the resized uint8 images in device memory
+and assemble each batch there; falls back to the host loader when the data set does not fit).  Multi-GPU: launch with
 ``python -m torch.distributed.run --nproc-per-node N main.py ...`` (one process per GPU, RCCL).
 """
 import argparse
@@ -54,12 +55,14 @@ def main(hparams):
         # one data set (one seed) for the whole job; the module shards it across the ranks
         data_module = SyntheticDataModule(n_train=hparams.synthetic, n_val=max(hparams.batch_size, 8),
                                           batch_size=hparams.batch_size, size=hparams.image_size,
-                                          seed=1234, world=world, rank=rank)
+                                          seed=1234, world=world, rank=rank, device_cache=hparams.device_cache,
+                                          device=device)
     else:
         # every rank reads its own shard of the lists (DistributedSampler semantics, as Lightning-DDP gives the
         # reference): an epoch is one pass over the data, not `world` passes
         data_module = ImageDataModule(hparams.data, hparams.val_data, batch_size=hparams.batch_size,
-                                      normalize=True, num_workers=hparams.num_workers, world=world, rank=rank)
+                                      normalize=True, num_workers=hparams.num_workers, world=world, rank=rank,
+                                      device_cache=hparams.device_cache, device=device)
 
     checkpoint_callback = ModelCheckpoint(save_top_k=1, monitor="val_ssim", mode="max", filename="best",
                                           save_last=False)
@@ -105,6 +108,8 @@ def build_parser():
                                  "resnext_unet", "trans_unet", "palette"])
     # build-only additions
     parser.add_argument("--synthetic", default=0, type=int, help="train on N synthetic pairs")
+    parser.add_argument("--device-cache", default=False, action="store_true",
+                        help="keep the decoded, resized data set in device memory and build every batch on the GPU")
     parser.add_argument("--image-size", default=256, type=int)
     parser.add_argument("--num-workers", default=0, type=int)
     return parser

@@ -3,6 +3,8 @@
 psnr_per_image.csv, mse_per_image.csv}); the eval-mode generator forward and the SSIM / PSNR / MSE
 arithmetic run on the MI355X kernels.
 
+Added (build-only) flag: --device-cache (resize the images on the GPU and read the batches from device memory).
+
 Reference defect handled here (SURVEY Q3): report.py:152 counts FLOPs with a 3-channel input;
 this counts the loaded model's own convolutions (1 "FLOP" per MAC, fvcore's convention).
 """
@@ -115,10 +117,12 @@ def main(hparams):
         raise NotImplementedError(f"model {hparams.model!r} is not built on the HIP path yet")
 
     if hparams.data is None:
-        data_module = SyntheticDataModule(n_val=16, batch_size=hparams.batch_size)
+        data_module = SyntheticDataModule(n_val=16, batch_size=hparams.batch_size, device_cache=hparams.device_cache,
+                                          device=dev)
         data_module.setup("predict")
     else:
-        data_module = ImageDataModule(hparams.data, batch_size=hparams.batch_size)
+        data_module = ImageDataModule(hparams.data, batch_size=hparams.batch_size, device_cache=hparams.device_cache,
+                                      device=dev)
         data_module.setup("predict")
     dataloader = data_module.predict_dataloader()
 
@@ -177,6 +181,8 @@ def build_parser():
     parser.add_argument("-m", "--model", default="pix2pix",
                         choices=["pix2pix", "attention_unet", "res18_unet", "res50_unet", "resv2_unet",
                                  "resnext_unet", "trans_unet", "palette", "identity"])
+    parser.add_argument("--device-cache", default=False, action="store_true",
+                        help="resize on the GPU and read the batches from device memory")
     return parser
 
 

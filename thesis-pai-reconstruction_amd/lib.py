@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PAI_HIP_LIB") or os.path.join(HERE, "libpai_hip.so")
 
 F32, BF16 = 0, 1
+U8 = 2          # PAI_U8: image bytes of the device-resident data set
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
 HINT_SOLO = 1
 
@@ -176,6 +177,9 @@ SIGNATURES = {
     "pai_filter_to_dense": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "pai_filter_grad_from_dense": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "pai_swap_mid": (_I, [_I, _P, C.c_int64, _I, _I, C.c_int64, _P, _P]),
+    "pai_resize_aa_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
+    "pai_batch_gather": (_I, [_I, _P, _P, _L, _L, _P, _I, _P, _P, _P, _P]),
+    "pai_data_kernel_name": (_I, [_I, _I, C.c_char_p, _I]),
 }
 
 _lib = None

@@ -285,7 +285,8 @@ class DevicePrefetcher:
     """Iterates a loader one batch AHEAD of the consumer: while step i runs, batch i + 1 is already being copied host ->
     device on a copy stream of its own (pinned staging, non_blocking), so the H2D transfer of 2 x N x 256 x 256 fp32
     never sits on the step's critical path (reference: Lightning moves each batch synchronously, main.py:136).
-    On a CPU "device" (tests) it is a plain pass-through."""
+    On a CPU "device" (tests) it is a plain pass-through.  A batch whose tensors already sit on the target device (a
+    ``dataset.DeviceLoader``) is handed on as it is: no pinning, no copy stream, no ``record_stream``."""
 
     def __init__(self, loader, device):
         self.loader, self.device = loader, device
@@ -299,6 +300,9 @@ class DevicePrefetcher:
             for batch in self.loader:
                 yield batch if dev is None else tuple(b.to(dev) if torch.is_tensor(b) else b for b in batch)
             return
+        tdev = torch.device(dev)
+        if tdev.index is None:
+            tdev = torch.device("cuda", torch.cuda.current_device())
         copy_stream = torch.cuda.Stream(dev)
         it = iter(self.loader)
 
@@ -306,6 +310,8 @@ class DevicePrefetcher:
             batch = next(it, None)
             if batch is None:
                 return None
+            if all(b.device == tdev for b in batch if torch.is_tensor(b)):
+                return batch, None               # built on the device, on the consumer's stream
             with torch.cuda.stream(copy_stream):
                 out = tuple((b if b.is_pinned() else b.pin_memory()).to(dev, non_blocking=True)
                             if torch.is_tensor(b) else b for b in batch)
@@ -316,11 +322,12 @@ class DevicePrefetcher:
         nxt = stage()
         while nxt is not None:
             cur, done = nxt
-            main = torch.cuda.current_stream(dev)
-            main.wait_event(done)
-            for b in cur:
-                if torch.is_tensor(b):
-                    b.record_stream(main)        # allocated on the copy stream, consumed on the main one
+            if done is not None:
+                main = torch.cuda.current_stream(dev)
+                main.wait_event(done)
+                for b in cur:
+                    if torch.is_tensor(b):
+                        b.record_stream(main)        # allocated on the copy stream, consumed on the main one
             nxt = stage()                        # the next copy is in flight while the caller trains on `cur`
             yield cur
 

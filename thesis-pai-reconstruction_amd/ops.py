@@ -8,11 +8,12 @@ from __future__ import annotations
 import ctypes as C
 
 import threading
+from typing import Optional
 
 import torch
 
 from . import lib as L
-from .lib import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, BF16, F32, ConvDesc, PaiError  # noqa: F401
+from .lib import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, BF16, F32, U8, ConvDesc, PaiError  # noqa: F401
 
 
 def code_of(dtype: torch.dtype) -> int:
@@ -994,3 +995,62 @@ class Comm:
         if self._h:
             L.check(L.load().pai_comm_destroy(self._h), "pai_comm_destroy")
             self._h = C.c_void_p()
+
+
+# ---- device-resident data set (csrc/data.hip) -----------------------------------------------------------------------
+def data_kernel_name(op: int, dtype: torch.dtype = torch.uint8) -> str:
+    """rocprofv3 symbol of the kernel behind ``resize_aa_u8`` (op 0) / ``batch_gather`` of a ``dtype`` cache (op 1)."""
+    buf = C.create_string_buffer(96)
+    if L.load().pai_data_kernel_name(op, U8 if dtype == torch.uint8 else code_of(dtype), buf, 96) != 0:
+        L.check(1, "pai_data_kernel_name")
+    return buf.value.decode()
+
+
+class AATables:
+    """Device copies of ``dataset.aa_tables(in_size, out_size)`` for ``resize_aa_u8`` (a few KB per size pair)."""
+
+    def __init__(self, bounds, weights, device):
+        self.host_bounds = bounds.to(torch.int32).contiguous()           # [out][2], read by the launcher on the host
+        self.bounds = self.host_bounds.to(device)
+        self.weights = weights.to(torch.float32).contiguous().to(device)  # [out][K]
+        self.K = int(weights.shape[1])
+
+
+def resize_aa_u8(src, out, wtab: Optional["AATables"], htab: Optional["AATables"]):
+    """``out`` uint8 [n, S, S] = the reference's resize of ``src`` uint8 [n, H, W] (pai_resize_aa_u8); a table is None
+    for an axis that already has S entries."""
+    if src.dim() != 3 or out.dim() != 3 or out.shape[0] != src.shape[0] or out.shape[1] != out.shape[2]:
+        raise PaiError(f"resize_aa_u8: [n, H, W] -> [n, S, S] expected, got {tuple(src.shape)} -> {tuple(out.shape)}")
+    if not (src.is_contiguous() and out.is_contiguous()):
+        raise PaiError("resize_aa_u8 needs contiguous tensors")
+    n, H, W = (int(v) for v in src.shape)
+    S = int(out.shape[1])
+    for tab in (wtab, htab):
+        if tab is not None and (tab.bounds.device != src.device or tab.bounds.shape[0] != S):
+            raise PaiError("resize_aa_u8: a table of another device or output size")
+    L.check(L.load().pai_resize_aa_u8(
+        _p(src, torch.uint8), n, H, W, S,
+        _p(wtab.bounds) if wtab else None, _p(wtab.weights) if wtab else None, wtab.K if wtab else 0,
+        _p(htab.bounds) if htab else None, _p(htab.weights) if htab else None, htab.K if htab else 0,
+        htab.host_bounds.data_ptr() if htab else None, _p(out, torch.uint8), _stream()), "pai_resize_aa_u8")
+    return out
+
+
+def batch_gather(cache_a, cache_b, indices, count: int, table, out_a, out_b):
+    """``out_a[b], out_b[b] = value(cache_a[indices[b]]), value(cache_b[indices[b]])`` for b < count in one launch
+    (pai_batch_gather).  Caches: uint8 (``table`` maps a byte to its fp32 value) or fp32 (copied), [M, ...]; ``indices``:
+    int64 on the device; outputs: fp32 [count, ...]."""
+    if cache_a.dtype != cache_b.dtype or cache_a.shape != cache_b.shape or cache_a.dtype not in (torch.uint8, torch.float32):
+        raise PaiError("batch_gather: two uint8 or two fp32 caches of one shape expected")
+    if not all(t.is_contiguous() for t in (cache_a, cache_b, indices, out_a, out_b)):
+        raise PaiError("batch_gather needs contiguous tensors")
+    M = int(cache_a.shape[0])
+    per = cache_a.numel() // max(M, 1)
+    if indices.numel() < count or out_a.numel() != count * per or out_b.numel() != count * per:
+        raise PaiError("batch_gather: indices / outputs do not hold `count` images")
+    u8 = cache_a.dtype == torch.uint8
+    if u8 and (table is None or table.numel() != 256):
+        raise PaiError("batch_gather: a uint8 cache needs the 256-entry fp32 value table")
+    L.check(L.load().pai_batch_gather(U8 if u8 else F32, _p(cache_a), _p(cache_b), M, per, _p(indices, torch.int64), int(count),
+                                      _p(table, torch.float32) if u8 else None, _p(out_a, torch.float32),
+                                      _p(out_b, torch.float32), _stream()), "pai_batch_gather")
