@@ -57,7 +57,8 @@ const char* pai_last_error(void);
  * 131: pai_lerp_multi (the EMA update of callbacks/ema.py), PAI_TUNE_<name> environment defaults of the tunables.
  * 132: input prologue (pai_conv_prologue_ok, pai_conv_fwd_pro, pai_conv_wgrad_pro); pai_instnorm_fwd / _bwd; pai_bn2_bwd_reduce / _apply; pai_bn_stats_buffer_rows grows for
  * layers with more than 2048 partial rows (callers that size the buffer through it need no change).
- * 133: device-resident data set (pai_resize_aa_u8, pai_batch_gather, pai_data_kernel_name), PAI_U8. */
+ * 133: device-resident data set (pai_resize_aa_u8, pai_batch_gather, pai_data_kernel_name), PAI_U8.
+ * 134: report evaluation (pai_eval_planes, pai_eval_kernel_name). */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -536,6 +537,17 @@ int pai_denormalize(const float* x, const float* grad_out_or_null, int64_t numel
  * out2[0] += sum over images (N*C planes) of the per-plane 5-px-cropped SSIM mean
  * out2[1] += sum of squared error over all pixels
  * per_image (fp64 [N*C], +=) and full_map (fp32 [N*C][H][W], un-cropped) optional.
+ *
+ * pai_eval_planes is the report's form of the same pass (report.py:78-96,188-233): sums per plane, images as bytes.
+ * ssim_plane[nc] += mean of the 5-px-cropped map of plane nc; sse_plane[nc] += its squared error (both fp64, caller zeroes).
+ * ssim_map_u8[nc][y][x] = (uint8)(clamp(S, 0, 1) * 255.999f), the un-cropped map with torchvision 0.15.1's float -> uint8
+ * conversion (models/utils.py:12); S is the same bits as pai_ssim_sse's full_map.
+ * hot_u8[nc][0..2][y][x] = lut_rgb[min((int)(x * 256.f), 255)][0..2] of the (denormalised) prediction x: matplotlib's
+ * lookup of a 256-entry colormap, the table ([256][3] bytes on the device) made by the caller; x < 0 takes entry 0, NaN
+ * gives 0, 0, 0.  Every output is optional (NULL), at least one is needed.  The byte outputs are 4-byte aligned and their
+ * allocations are padded to a multiple of 4 bytes: they are written as whole 32-bit words, merged atomically where a word
+ * straddles two rows (W % 4 != 0).  NC <= 65535.  Depth strips: a contiguous [N][C][H][W] tensor with H % 16 == 0 is
+ * [N*C*16][H/16][W].  pai_eval_kernel_name: symbol of the kernel behind op 0 (pai_eval_planes), as pai_conv_kernel_name.
  * ------------------------------------------------------------------------- */
 int pai_ssim_sse(const float* pred, const float* target, int NC, int H, int W, int denorm,
                  double* out2, double* per_image, float* full_map, void* stream);
@@ -546,6 +558,10 @@ int pai_ssim_psnr_bwd(const float* pred, const float* target, int NC, int H, int
                       float w_ssim, float w_psnr, const double* sse, float* grad, float* workspace,
                       void* stream);
 int64_t pai_ssim_bwd_workspace_floats(int NC, int H, int W);
+int pai_eval_planes(const float* pred, const float* target, int NC, int H, int W, int denorm,
+                    double* ssim_plane, double* sse_plane, unsigned char* ssim_map_u8,
+                    const unsigned char* lut_rgb, unsigned char* hot_u8, void* stream);
+int pai_eval_kernel_name(int op, char* name, int name_len);
 
 /* ---------------------------------------------------------------------------
  * Utilities

@@ -293,6 +293,11 @@ int launch_wgrad_slab_sum(float* dw, const float* slab, int nsplits, int64_t n, 
 bool grouped3_wgrad_ok(int dtype, const GG& g, const float* dbias);
 int64_t grouped3_wgrad_part_bytes(const GG& g);
 int launch_grouped3_wgrad(const GG& g, const WgradArgs& a, float* part, hipStream_t s);
+// report evaluation kernel (ssim.hip: it shares the tile stages of ssim_k; entry point pai_eval_planes in eval.hip)
+int launch_eval_planes(const float* pred, const float* target, int NC, int H, int W, int denorm, double* ssim_plane,
+                       double* sse_plane, unsigned char* map_u8, const unsigned char* lut_rgb, unsigned char* hot_u8,
+                       hipStream_t stream);
+const char* eval_planes_kernel_name();
 // patch-resident weight gradient with 128 x 64 / 64 x 128 wave tiles (gg_wg3.hip)
 bool wgrad3_ok(const GG& g);
 int launch_wgrad3(const GG& g, const WgradArgs& a, hipStream_t s);

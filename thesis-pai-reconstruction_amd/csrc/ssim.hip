@@ -60,51 +60,42 @@ __device__ __forceinline__ void block_add2(double a, double b, double* da, doubl
     }
 }
 
-// MODE 0: forward metrics.  MODE 1: write the three gradient maps (backward pass 1).
-template <int MODE>
-__global__ __launch_bounds__(256) void ssim_k(const float* pred, const float* target, int H, int W, int denorm,
-                                              Gauss gk, double inv_crop, double* out2, double* per_image,
-                                              float* full_map, float* dmaps, int NC, float wscale, int xtiles) {
-    __shared__ float P[TI][TI + 1], T[TI][TI + 1];
-    __shared__ float Hb[5][TI][TS];
+// ---- the stages of one 32 x 32 output tile, shared by ssim_k and eval_planes_k (one source: the per-pixel S of the two
+// kernels is the same bits) -----------------------------------------------------------------------------------------------
+typedef float TileIn[TI][TI + 1];
+typedef float TileH[5][TI][TS];
+
+// stage 1: the 42 x 42 input window of both images (reflect padded, optionally denormalised) into LDS
+__device__ __forceinline__ void ssim_tile_fill(const float* p, const float* t, int H, int W, int y0, int x0, int denorm,
+                                               TileIn& P, TileIn& T) {
     const int tid = threadIdx.x;
-    const int nc = blockIdx.z;
-    const int y0 = blockIdx.y * TS;
-    const float* p = pred + (size_t)nc * H * W;
-    const float* t = target + (size_t)nc * H * W;
-    // One workgroup walks `xtiles` 32-pixel tiles of its tile row (MODE 0: the whole row, so that the three fp64
-    // atomics per workgroup -- all workgroups add to the same two or three words -- happen 512 instead of 4096
-    // times per 64-image batch: same-address atomics serialise at the memory side and were most of the 154 us)
-    double acc = 0.0, sse = 0.0;
-    for (int xt = blockIdx.x * xtiles; xt < (blockIdx.x + 1) * xtiles && xt * TS < W; ++xt) {
-    const int x0 = xt * TS;
-    if (xt != blockIdx.x * xtiles) __syncthreads();      // the previous tile's readers are done with P, T, Hb
-    {
-        // all 2 x 7 loads of a thread are issued before the first one is consumed: written as "load, store to LDS,
-        // next" the loop was seven dependent HBM round trips per tile
-        constexpr int NL = (TI * TI + 255) / 256;
-        float pv[NL], tv[NL];
+    // all 2 x 7 loads of a thread are issued before the first one is consumed: written as "load, store to LDS,
+    // next" the loop was seven dependent HBM round trips per tile
+    constexpr int NL = (TI * TI + 255) / 256;
+    float pv[NL], tv[NL];
 #pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int idx = tid + 256 * i;
-            const int r = idx / TI, c = idx - r * TI;
-            const int gy = reflect_idx(y0 - PADW + (idx < TI * TI ? r : 0), H), gx = reflect_idx(x0 - PADW + c, W);
-            pv[i] = p[(size_t)gy * W + gx];
-            tv[i] = t[(size_t)gy * W + gx];
-        }
+    for (int i = 0; i < NL; ++i) {
+        const int idx = tid + 256 * i;
+        const int r = idx / TI, c = idx - r * TI;
+        const int gy = reflect_idx(y0 - PADW + (idx < TI * TI ? r : 0), H), gx = reflect_idx(x0 - PADW + c, W);
+        pv[i] = p[(size_t)gy * W + gx];
+        tv[i] = t[(size_t)gy * W + gx];
+    }
 #pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int idx = tid + 256 * i;
-            const int r = idx / TI, c = idx - r * TI;
-            if (idx < TI * TI) {
-                P[r][c] = denorm_val(pv[i], denorm);
-                T[r][c] = denorm_val(tv[i], denorm);
-            }
+    for (int i = 0; i < NL; ++i) {
+        const int idx = tid + 256 * i;
+        const int r = idx / TI, c = idx - r * TI;
+        if (idx < TI * TI) {
+            P[r][c] = denorm_val(pv[i], denorm);
+            T[r][c] = denorm_val(tv[i], denorm);
         }
     }
-    __syncthreads();
-    // horizontal pass, four neighbouring outputs per thread from one 14-value window: a third of the LDS reads and
-    // of the products a*a, b*b, a*b of the one-output-per-thread form (the kernel is instruction-bound, not HBM-bound)
+}
+
+// stage 2: horizontal pass, four neighbouring outputs per thread from one 14-value window: a third of the LDS reads and
+// of the products a*a, b*b, a*b of the one-output-per-thread form (the kernel is instruction-bound, not HBM-bound)
+__device__ __forceinline__ void ssim_tile_hpass(const TileIn& P, const TileIn& T, TileH& Hb, const Gauss& gk) {
+    const int tid = threadIdx.x;
     for (int idx = tid; idx < TI * (TS / 4); idx += 256) {
         const int r = idx / (TS / 4), c = (idx - r * (TS / 4)) * 4;
         float wa[KS + 3], wb[KS + 3];
@@ -133,35 +124,72 @@ __global__ __launch_bounds__(256) void ssim_k(const float* pred, const float* ta
             Hb[4][r][c + o] = spt[o];
         }
     }
-    __syncthreads();
-    // vertical pass: a thread owns column ox and the four rows 4 (tid >> 5) .. +3, one 14-row window per map
-    float vm[5][4];
-    {
-        const int oyb = (tid >> 5) * 4, ox = tid & 31;
+}
+
+// stage 3: vertical pass: a thread owns column ox and the four rows 4 (tid >> 5) .. +3, one 14-row window per map
+__device__ __forceinline__ void ssim_tile_vpass(const TileH& Hb, const Gauss& gk, float (&vm)[5][4]) {
+    const int tid = threadIdx.x;
+    const int oyb = (tid >> 5) * 4, ox = tid & 31;
 #pragma unroll
-        for (int m = 0; m < 5; ++m) {
-            float w[KS + 3];
+    for (int m = 0; m < 5; ++m) {
+        float w[KS + 3];
 #pragma unroll
-            for (int k = 0; k < KS + 3; ++k) w[k] = Hb[m][oyb + k][ox];
+        for (int k = 0; k < KS + 3; ++k) w[k] = Hb[m][oyb + k][ox];
 #pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                float acc_ = 0.f;
+        for (int o = 0; o < 4; ++o) {
+            float acc_ = 0.f;
 #pragma unroll
-                for (int k = 0; k < KS; ++k) acc_ = fmaf(gk.g[k], w[o + k], acc_);
-                vm[m][o] = acc_;
-            }
+            for (int k = 0; k < KS; ++k) acc_ = fmaf(gk.g[k], w[o + k], acc_);
+            vm[m][o] = acc_;
         }
     }
+}
+
+// stage 4: the SSIM value of output row j of the thread and the factors the gradient needs
+struct SsimPix { float mp, mt, A1, A2, B1, B2, S; };
+__device__ __forceinline__ SsimPix ssim_pix(const float (&vm)[5][4], int j) {
+    SsimPix q;
+    q.mp = vm[0][j]; q.mt = vm[1][j];
+    const float mp = q.mp, mt = q.mt, epp = vm[2][j], ett = vm[3][j], ept = vm[4][j];
+    const float spp = epp - mp * mp, stt = ett - mt * mt, spt = ept - mp * mt;
+    q.A1 = 2.f * mp * mt + SSIM_C1; q.A2 = 2.f * spt + SSIM_C2;
+    q.B1 = mp * mp + mt * mt + SSIM_C1; q.B2 = spp + stt + SSIM_C2;
+    q.S = (q.A1 * q.A2) / (q.B1 * q.B2);
+    return q;
+}
+
+// MODE 0: forward metrics.  MODE 1: write the three gradient maps (backward pass 1).
+template <int MODE>
+__global__ __launch_bounds__(256) void ssim_k(const float* pred, const float* target, int H, int W, int denorm,
+                                              Gauss gk, double inv_crop, double* out2, double* per_image,
+                                              float* full_map, float* dmaps, int NC, float wscale, int xtiles) {
+    __shared__ TileIn P, T;
+    __shared__ TileH Hb;
+    const int tid = threadIdx.x;
+    const int nc = blockIdx.z;
+    const int y0 = blockIdx.y * TS;
+    const float* p = pred + (size_t)nc * H * W;
+    const float* t = target + (size_t)nc * H * W;
+    // One workgroup walks `xtiles` 32-pixel tiles of its tile row (MODE 0: the whole row, so that the three fp64
+    // atomics per workgroup -- all workgroups add to the same two or three words -- happen 512 instead of 4096
+    // times per 64-image batch: same-address atomics serialise at the memory side and were most of the 154 us)
+    double acc = 0.0, sse = 0.0;
+    for (int xt = blockIdx.x * xtiles; xt < (blockIdx.x + 1) * xtiles && xt * TS < W; ++xt) {
+    const int x0 = xt * TS;
+    if (xt != blockIdx.x * xtiles) __syncthreads();      // the previous tile's readers are done with P, T, Hb
+    ssim_tile_fill(p, t, H, W, y0, x0, denorm, P, T);
+    __syncthreads();
+    ssim_tile_hpass(P, T, Hb, gk);
+    __syncthreads();
+    float vm[5][4];
+    ssim_tile_vpass(Hb, gk, vm);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int oy = (tid >> 5) * 4 + j, ox = tid & 31;
         const int y = y0 + oy, x = x0 + ox;
         if (y >= H || x >= W) continue;
-        const float mp = vm[0][j], mt = vm[1][j], epp = vm[2][j], ett = vm[3][j], ept = vm[4][j];
-        const float spp = epp - mp * mp, stt = ett - mt * mt, spt = ept - mp * mt;
-        const float A1 = 2.f * mp * mt + SSIM_C1, A2 = 2.f * spt + SSIM_C2;
-        const float B1 = mp * mp + mt * mt + SSIM_C1, B2 = spp + stt + SSIM_C2;
-        const float S = (A1 * A2) / (B1 * B2);
+        const SsimPix q = ssim_pix(vm, j);
+        const float mp = q.mp, mt = q.mt, A1 = q.A1, A2 = q.A2, B1 = q.B1, B2 = q.B2, S = q.S;
         const bool in_crop = y >= PADW && y < H - PADW && x >= PADW && x < W - PADW;
         if (MODE == 0) {
             if (full_map) full_map[((size_t)nc * H + y) * W + x] = S;
@@ -203,6 +231,123 @@ extern "C" int pai_ssim_sse(const float* pred, const float* target, int NC, int 
     dim3 grid(cdiv(xt_all, xtiles), cdiv(H, TS), NC);
     PAI_LAUNCH(ssim_k<0>, grid, dim3(256), 0, (hipStream_t)stream, pred, target, H, W, denorm, gk,
                        inv_crop, out2, per_image, full_map, (float*)nullptr, NC, 0.f, xtiles);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- report evaluation (pai_eval_planes, entry point in eval.hip) --------------------------------------------------------
+// ssim_k<0>'s pass with per-plane sums and 8-bit outputs: the SSIM map as to_int(clamp(S, 0, 1)) and the prediction through
+// a 256-entry RGB table.  The bytes of a tile are staged in LDS and leave as 32-bit words.
+typedef unsigned char TileU8[TS][TS];
+
+// One staged 32 x 32 byte tile -> rows y0.., columns x0.. of a [H][W] byte plane.  `aligned` (plane base and W multiples of
+// 4): every word of the tile lies fully inside or fully outside the plane, one plain store per thread.  Otherwise a row
+// starts at any byte: up to 9 words per tile row, whole ones stored, the partial ones at both ends merged with a 32-bit
+// atomic and / or pair (the other bytes of such a word belong to the neighbouring tile, row or plane, maybe of another
+// workgroup; the last word of the buffer may reach into its padding).
+__device__ __forceinline__ void store_tile_u8(const TileU8& st, unsigned char* plane, int H, int W, int y0, int x0, bool aligned) {
+    const int tid = threadIdx.x;
+    if (aligned) {
+        const int r = tid >> 3, c = (tid & 7) * 4;
+        if (y0 + r < H && x0 + c < W)
+            *(unsigned*)(plane + (size_t)(y0 + r) * W + x0 + c) = *(const unsigned*)&st[r][c];
+        return;
+    }
+    const int cols = min(TS, W - x0);
+    for (int i = tid; i < TS * 9; i += 256) {
+        const int r = i / 9, k = i - r * 9;
+        if (y0 + r >= H) continue;
+        const uintptr_t s = (uintptr_t)(plane + (size_t)(y0 + r) * W + x0), e = s + cols;
+        const uintptr_t w0 = ((s >> 2) + k) << 2;                // this word covers bytes [w0, w0 + 4)
+        const uintptr_t lo = max(w0, s), hi = min(w0 + 4, e);
+        if (lo >= hi) continue;
+        unsigned v = 0, mask = 0;
+        for (uintptr_t b = lo; b < hi; ++b) {
+            v |= (unsigned)st[r][b - s] << (8 * (b - w0));
+            mask |= 0xffu << (8 * (b - w0));
+        }
+        unsigned* dst = (unsigned*)w0;
+        if (mask == 0xffffffffu) {
+            *dst = v;
+        } else {
+            atomicAnd(dst, ~mask);
+            atomicOr(dst, v);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void eval_planes_k(const float* pred, const float* target, int H, int W, int denorm,
+                                                     Gauss gk, double inv_crop, double* ssim_plane, double* sse_plane,
+                                                     unsigned char* map_u8, const unsigned char* lut_rgb,
+                                                     unsigned char* hot_u8, int xtiles, int aligned) {
+    __shared__ TileIn P, T;
+    __shared__ TileH Hb;
+    __shared__ __align__(16) TileU8 st[4];                 // SSIM map, R, G, B
+    __shared__ unsigned lut[256];            // R | G << 8 | B << 16
+    const int tid = threadIdx.x;
+    const int nc = blockIdx.z;
+    const int y0 = blockIdx.y * TS;
+    const float* p = pred + (size_t)nc * H * W;
+    const float* t = target + (size_t)nc * H * W;
+    const size_t plane = (size_t)H * W;
+    if (hot_u8) lut[tid] = lut_rgb[3 * tid] | (unsigned)lut_rgb[3 * tid + 1] << 8 | (unsigned)lut_rgb[3 * tid + 2] << 16;
+    double acc = 0.0, sse = 0.0;
+    for (int xt = blockIdx.x * xtiles; xt < (blockIdx.x + 1) * xtiles && xt * TS < W; ++xt) {
+        const int x0 = xt * TS;
+        if (xt != blockIdx.x * xtiles) __syncthreads();      // the previous tile's readers are done with P, T, Hb, st
+        ssim_tile_fill(p, t, H, W, y0, x0, denorm, P, T);
+        __syncthreads();
+        ssim_tile_hpass(P, T, Hb, gk);
+        __syncthreads();
+        float vm[5][4];
+        ssim_tile_vpass(Hb, gk, vm);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int oy = (tid >> 5) * 4 + j, ox = tid & 31;
+            const int y = y0 + oy, x = x0 + ox;
+            if (y >= H || x >= W) continue;
+            const float S = ssim_pix(vm, j).S;
+            if (y >= PADW && y < H - PADW && x >= PADW && x < W - PADW) acc += (double)S;
+            const float pv = P[oy + PADW][ox + PADW];
+            const float d = pv - T[oy + PADW][ox + PADW];
+            sse += (double)d * d;
+            if (map_u8) st[0][oy][ox] = (unsigned char)__fmul_rn(fminf(fmaxf(S, 0.f), 1.f), 255.999f);
+            if (hot_u8) {
+                // matplotlib's Colormap.__call__ on floats: int(x * N) clipped to the table, NaN -> the "bad" colour (black)
+                const unsigned c = pv != pv ? 0u : lut[min(max((int)(pv * 256.f), 0), 255)];
+                st[1][oy][ox] = (unsigned char)c;
+                st[2][oy][ox] = (unsigned char)(c >> 8);
+                st[3][oy][ox] = (unsigned char)(c >> 16);
+            }
+        }
+        if (map_u8 || hot_u8) {
+            __syncthreads();
+            if (map_u8) store_tile_u8(st[0], map_u8 + (size_t)nc * plane, H, W, y0, x0, aligned);
+            if (hot_u8) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch)
+                    store_tile_u8(st[1 + ch], hot_u8 + ((size_t)nc * 3 + ch) * plane, H, W, y0, x0, aligned);
+            }
+        }
+    }
+    // one addition per workgroup and sum, to the words of its own plane
+    block_add2(acc * inv_crop, sse, ssim_plane ? ssim_plane + nc : nullptr, sse_plane ? sse_plane + nc : nullptr, nullptr);
+}
+
+const char* eval_planes_kernel_name() { return "eval_planes_k"; }
+
+int launch_eval_planes(const float* pred, const float* target, int NC, int H, int W, int denorm, double* ssim_plane,
+                       double* sse_plane, unsigned char* map_u8, const unsigned char* lut_rgb, unsigned char* hot_u8,
+                       hipStream_t stream) {
+    static const Gauss gk = make_gauss();
+    const double inv_crop = 1.0 / ((double)(H - 2 * PADW) * (double)(W - 2 * PADW));
+    // whole tile rows per workgroup, as ssim_k<0> (very wide images: eight tiles each)
+    const int xt_all = cdiv(W, TS);
+    const int xtiles = xt_all < 8 ? xt_all : 8;
+    const int aligned = W % 4 == 0 && (((uintptr_t)map_u8 | (uintptr_t)hot_u8) & 3) == 0;
+    dim3 grid(cdiv(xt_all, xtiles), cdiv(H, TS), NC);
+    PAI_LAUNCH(eval_planes_k, grid, dim3(256), 0, stream, pred, target, H, W, denorm, gk, inv_crop, ssim_plane, sse_plane,
+               map_u8, lut_rgb, hot_u8, xtiles, aligned);
     PAI_LAUNCH_CHECK();
     return 0;
 }

@@ -456,3 +456,67 @@ def ssim_per_image(pred, target, return_full_image=False):
     n, c = p.shape[:2]
     vals = per.view(n, c).mean(dim=1).float()
     return (vals, fm) if return_full_image else vals
+
+
+# --------------------------------------------------------------------------------------
+# report evaluation: per-image metrics and the rendered images of a chunk, on the device
+# --------------------------------------------------------------------------------------
+_AFMHOT = {}
+
+
+def afmhot_lut_u8(device=None) -> torch.Tensor:
+    """The 256 colours of matplotlib's ``afmhot`` as uint8 [256, 3], converted like every image the report writes
+    (models/utils.py:to_int).  Indexed with ``min(int(x * 256), 255)`` it gives the bytes of reference report.py:220-233
+    for a float image x in [0, 1].  Built once on the host; ``device``: a cached copy there."""
+    key = str(device) if device is not None else "host"
+    if "host" not in _AFMHOT:
+        import numpy as np
+        from matplotlib import colormaps
+
+        from .models.utils import to_int
+        _AFMHOT["host"] = to_int(torch.tensor(colormaps["afmhot"](np.arange(256))[:, :3], dtype=torch.float32)).contiguous()
+    if key not in _AFMHOT:
+        _AFMHOT[key] = _AFMHOT["host"].to(device)
+    return _AFMHOT[key]
+
+
+class EvalImages:
+    """Result of ``eval_images``: ``ssim`` / ``psnr`` / ``mse`` fp32 [N], ``sse`` fp64 [N] (squared error per image),
+    ``strip_ssim`` fp32 [N, strips] or None, ``ssim_map_u8`` uint8 [N, C, H, W] or None, ``hot_u8`` uint8 [N, C, 3, H, W]
+    or None."""
+    __slots__ = ("ssim", "psnr", "mse", "sse", "strip_ssim", "ssim_map_u8", "hot_u8")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def eval_images(pred, target, denorm=False, strips=0, ssim_map=False, hot=False) -> EvalImages:
+    """What the report computes for a chunk of images (reference report.py:78-96,188-233) in two launches, whatever N is:
+    one pass over the whole images (per-plane SSIM and squared error, the SSIM map and the afmhot rendering as bytes), one
+    over the ``strips`` horizontal strips of every plane.  ``denorm``: the inputs are raw network output / targets in
+    [-1, 1] (models/utils.py:11 is fused).  The per-image values are the report's expressions, in fp64 over the per-plane
+    sums, rounded once to fp32."""
+    _check_f32_cuda(pred, target)
+    p, t = pred.detach().contiguous().float(), target.detach().contiguous().float()
+    if p.dim() != 4 or p.shape != t.shape:
+        raise ops.PaiError(f"eval_images: two [N, C, H, W] tensors of one shape expected, got {tuple(p.shape)}, {tuple(t.shape)}")
+    n, c, h, w = (int(v) for v in p.shape)
+    strips = int(strips)
+    if strips and h % strips:
+        raise ops.PaiError(f"eval_images: H = {h} is not a multiple of {strips} strips")
+    sums = torch.zeros(2 * n * c + n * c * strips, dtype=torch.float64, device=p.device)
+    ssim_pl, sse_pl, strip_pl = sums[:n * c], sums[n * c:2 * n * c], sums[2 * n * c:]
+    map_u8 = ops.padded_u8((n, c, h, w), p.device) if ssim_map else None
+    hot_u8 = ops.padded_u8((n, c, 3, h, w), p.device) if hot else None
+    ops.eval_planes(p, t, n * c, h, w, denorm, ssim_pl, sse_pl, map_u8, afmhot_lut_u8(p.device) if hot else None, hot_u8)
+    if strips:      # [N, C, H, W] is [N * C * strips, H / strips, W]
+        ops.eval_planes(p, t, n * c * strips, h // strips, w, denorm, strip_pl)
+    sse = sse_pl.view(n, c).sum(dim=1)
+    numel = c * h * w
+    return EvalImages(ssim=ssim_pl.view(n, c).mean(dim=1).float(),
+                      psnr=(-torch.log(sse / numel) * (10.0 / math.log(10.0))).float(),
+                      mse=torch.sqrt(sse / numel).float() ** 2,
+                      sse=sse,
+                      strip_ssim=strip_pl.view(n, c, strips).mean(dim=1).float() if strips else None,
+                      ssim_map_u8=map_u8, hot_u8=hot_u8)

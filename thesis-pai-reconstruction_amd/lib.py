@@ -144,6 +144,8 @@ SIGNATURES = {
     "pai_ssim_sse": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pai_ssim_psnr_bwd": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
     "pai_ssim_bwd_workspace_floats": (_L, [_I, _I, _I]),
+    "pai_eval_planes": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "pai_eval_kernel_name": (_I, [_I, C.c_char_p, _I]),
     "pai_cast": (_I, [_I, _P, _I, _P, _L, _P]),
     "pai_reduce_rows": (_I, [_P, _I, _I, _P, _I, _P]),
     "pai_adam": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _P]),

@@ -716,6 +716,55 @@ def ssim_sse(pred, target, NC, H, W, denorm, out2=None, per_image=None, full_map
                                   _p(full_map, torch.float32), _stream()), "pai_ssim_sse")
 
 
+def eval_kernel_name(op: int = 0) -> str:
+    """rocprofv3 symbol of the kernel behind ``eval_planes`` (op 0)."""
+    buf = C.create_string_buffer(96)
+    if L.load().pai_eval_kernel_name(op, buf, 96) != 0:
+        L.check(1, "pai_eval_kernel_name")
+    return buf.value.decode()
+
+
+def padded_u8(shape, device) -> torch.Tensor:
+    """uint8 tensor of ``shape`` whose allocation is a multiple of 4 bytes: ``eval_planes`` writes whole 32-bit words."""
+    n = 1
+    for v in shape:
+        n *= int(v)
+    return torch.empty((n + 3) // 4 * 4, dtype=torch.uint8, device=device)[:n].view(*shape)
+
+
+def eval_planes(pred, target, NC: int, H: int, W: int, denorm, ssim_plane=None, sse_plane=None, ssim_map_u8=None,
+                lut_rgb=None, hot_u8=None):
+    """One pass over the NC planes [H, W] of a pair (pai_eval_planes): ``ssim_plane`` / ``sse_plane`` fp64 [NC] (+=),
+    ``ssim_map_u8`` uint8 [NC, H, W], ``hot_u8`` uint8 [NC, 3, H, W] = ``lut_rgb`` (uint8 [256, 3]) of the prediction; every
+    output optional.  The byte outputs come from ``padded_u8``."""
+    given = [t for t in (pred, target, ssim_plane, sse_plane, ssim_map_u8, lut_rgb, hot_u8) if t is not None]
+    if not all(t.is_cuda for t in given):
+        raise PaiError("eval_planes needs HIP device tensors (no CPU fallback exists)")
+    if not all(t.is_contiguous() and t.device == pred.device for t in given):
+        raise PaiError("eval_planes needs contiguous tensors of one device")
+    NC, H, W = int(NC), int(H), int(W)
+    if pred.numel() != NC * H * W or target.numel() != NC * H * W:
+        raise PaiError(f"eval_planes: pred / target do not hold {NC} planes of {H} x {W}")
+    if ssim_plane is None and sse_plane is None and ssim_map_u8 is None and hot_u8 is None:
+        raise PaiError("eval_planes: no output given")
+    for t in (ssim_plane, sse_plane):
+        if t is not None and t.numel() != NC:
+            raise PaiError(f"eval_planes: a per-plane sum of {t.numel()} entries for {NC} planes")
+    for t, per in ((ssim_map_u8, 1), (hot_u8, 3)):
+        if t is None:
+            continue
+        if t.numel() != per * NC * H * W:
+            raise PaiError(f"eval_planes: a byte output of {t.numel()} bytes, {per * NC * H * W} expected")
+        if t.untyped_storage().nbytes() - t.storage_offset() < (t.numel() + 3) // 4 * 4 or t.data_ptr() % 4:
+            raise PaiError("eval_planes: byte outputs are 4-byte aligned and padded to a multiple of 4 bytes (ops.padded_u8)")
+    if hot_u8 is not None and (lut_rgb is None or tuple(lut_rgb.shape) != (256, 3)):
+        raise PaiError("eval_planes: hot_u8 needs the [256, 3] uint8 colour table")
+    L.check(L.load().pai_eval_planes(_p(pred, torch.float32), _p(target, torch.float32), NC, H, W, int(denorm),
+                                     _p(ssim_plane, torch.float64), _p(sse_plane, torch.float64),
+                                     _p(ssim_map_u8, torch.uint8), _p(lut_rgb, torch.uint8), _p(hot_u8, torch.uint8),
+                                     _stream()), "pai_eval_planes")
+
+
 def ssim_bwd_workspace_floats(NC, H, W) -> int:
     return L.load().pai_ssim_bwd_workspace_floats(NC, H, W)
 
