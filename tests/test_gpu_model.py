@@ -414,7 +414,9 @@ def test_weight_gradients_issued_in_threes_equal_those_issued_one_by_one(pai, mo
     pass is the same -- bit for bit on the dense layers' weights (slab sums in split order), to rounding noise where fp32
     atomics add (bias gradients, thin layers)."""
     mults, seed = (1, 2, 2, 4), 41
-    x, t = synth_batch(seed + 100, 4, 32)           # 4 x 16 x 16 output pixels and fewer: every layer is a held one
+    # every layer below the head has 4 x 16 x 16 output pixels or fewer and is a held one; the head has 4 x 32 x 32 = 4096,
+    # above PAI_WGRAD_BATCH_PIX, and is issued at once (the held head: test_held_head_... below)
+    x, t = synth_batch(seed + 100, 4, 32)
     batch = (x.to(DEV), t.to(DEV))
     monkeypatch.setenv("PAI_NO_STREAM_ADAM", "1")   # gradients stay in the arena until step()
     grads = []
@@ -439,6 +441,75 @@ def test_weight_gradients_issued_in_threes_equal_those_issued_one_by_one(pai, mo
             a, n = arena.offsets[id(conv.weight)]
             assert torch.equal(g[a:a + n], g1[a:a + n]), conv
 
+
+@pytest.mark.parametrize("n,size,loss_type", [(1, 32, "gan"), (4, 16, "mse")], ids=["1x32x32_gan", "4x16x16_mse"])
+def test_held_head_weight_gradient_precedes_scratch_event_and_tail_fork(pai, monkeypatch, n, size, loss_type):
+    """A head of at most PAI_WGRAD_BATCH_PIX (1024) output pixels is a HELD weight gradient: wgrad() only queues it.  Its
+    thin kernel and encoder 0's (on the tail stream) both use the tail of the registered scratch buffer, so the order of
+    issue has to be: head launch on the side stream -> scratch event recorded on that stream -> fork_tail() with the event
+    marked, which makes the tail stream wait for it.  First step of a fresh model: the side stream does not exist yet when
+    wgrad() returns.  (A PatchGAN needs 32 x 32 inputs, so the 16 x 16 batch trains against the MSE loss.)
+    Then the gradients of that step against a run without any overlap (PAI_NO_OVERLAP=1): dense weights bit for bit, thin
+    layers and biases (fp32 atomics) to 1e-5 of the largest gradient, as in the batching test above."""
+    from thesis_pai_reconstruction_amd import engine as E, ops
+    mults, seed = (1, 2), 43
+    x, t = synth_batch(seed + 100, n, size)
+    batch = (x.to(DEV), t.to(DEV))
+    monkeypatch.setenv("PAI_NO_STREAM_ADAM", "1")   # gradients stay in the arena until step()
+    log = []
+    orig_wgrad, orig_record, orig_tail = ops.conv_wgrad, ops.Event.record, E._SideStream.fork_tail
+
+    def spy_wgrad(d, *a, **k):
+        if d.transposed and d.Cout == 1:
+            log.append(("head", None, ops._stream()))
+        return orig_wgrad(d, *a, **k)
+
+    def spy_record(self, stream=None):
+        log.append(("record", self, ops._raw(stream) if stream is not None else ops._stream()))
+        return orig_record(self, stream)
+
+    def spy_tail(self):
+        log.append(("fork_tail", self, self._scratch_marked))
+        return orig_tail(self)
+
+    monkeypatch.setattr(ops, "conv_wgrad", spy_wgrad)
+    monkeypatch.setattr(ops.Event, "record", spy_record)
+    monkeypatch.setattr(E._SideStream, "fork_tail", spy_tail)
+
+    def one_step():
+        m, _, _ = build(pai, mults, loss_type, seed, dtype=torch.bfloat16)
+        og = m.optimizers()
+        og = og[0] if isinstance(og, (list, tuple)) else og
+        seen = []
+        orig = og.step
+        og.step = lambda *a, orig=orig, og=og, **k: seen.append(og._engine.arena().flat.clone()) or orig(*a, **k)
+        del log[:]
+        m.training_step(batch, 0)
+        torch.cuda.synchronize()
+        assert len(seen) == 1 and torch.isfinite(seen[0]).all()
+        return seen[0], m.unet.engine
+
+    g, eng = one_step()
+    side = eng._side
+    assert side.on and side.stream is not None
+    heads = [i for i, e in enumerate(log) if e[0] == "head"]
+    recs = [i for i, e in enumerate(log) if e[0] == "record" and e[1] is side.scratch_ev]      # none while there is no event
+    tails = [i for i, e in enumerate(log) if e[0] == "fork_tail" and e[1] is side]
+    assert len(heads) == 1 and len(tails) == 1, log
+    assert log[heads[0]][2] == side.stream.cuda_stream, "the head's weight gradient runs on the side stream"
+    assert recs and heads[0] < recs[0] < tails[0], ("head launch -> scratch event -> fork_tail", [e[0] for e in log])
+    assert log[recs[0]][2] == log[heads[0]][2], "the event is recorded on the stream of the head's launch"
+    assert log[tails[0]][2] is True, "_scratch_marked when fork_tail() runs"
+
+    monkeypatch.setenv("PAI_NO_OVERLAP", "1")
+    g1, eng1 = one_step()
+    assert not eng1._side.on and not [e for e in log if e[0] == "record" and e[1] is eng1._side.scratch_ev]
+    scale = float(g1.abs().max())
+    assert float((g - g1).abs().max()) <= 1e-5 * scale
+    arena = eng1.arena()
+    for conv in eng1.enc_conv[1:] + eng1.dec_conv[:-1]:
+        a, cnt = arena.offsets[id(conv.weight)]
+        assert torch.equal(g[a:a + cnt], g1[a:a + cnt]), conv
 
 
 def test_dropout2d_step_matches_reference_fixture(pai, golden_dir):

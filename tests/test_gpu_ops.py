@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import oracle
-from _gpu_util import dev, from_nhwc, nhwc, q, rel_err, rnd
+from _gpu_util import dev, from_nhwc, max_err, nhwc, q, rel_err, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -184,6 +184,41 @@ def test_ssim_psnr_loss_gradient(pai, weights):
     got.backward()
     assert abs(float(got) - float(want)) < 2e-5 * max(1.0, abs(float(want)))
     assert rel_err(xg.grad.cpu(), xr.grad) < 2e-4
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("numel", [1, 7, 4096 + 3])
+@pytest.mark.parametrize("which", ["both", "a_only", "b_only"])
+def test_tanh_bwd(pai, dtype, numel, which):
+    """pai_tanh_bwd, the head's backward with up to two incoming gradients: dh = (g_a + g_b) * (1 - pred^2) against fp64
+    of exactly the fp32 inputs.  fp32: three or four roundings of magnitudes <= max|g_a + g_b|, bound 1e-6 of max|ref|;
+    bf16: one rounding of that fp32 value to 8 bits of mantissa (2^-8 relative) plus fp32 noise near zero.  pred holds
+    exact +-1 (saturated tanh: zero gradient) and 0; numel 1, 7 and one past four 1024-element blocks."""
+    from thesis_pai_reconstruction_amd import ops
+    rng = np.random.default_rng(numel)
+    pred = np.tanh(rng.standard_normal(numel) * 2).astype(np.float32)
+    if numel > 1:       # (the single element stays a generic value)
+        for i, v in zip(range(0, numel, max(1, numel // 5)), (1.0, -1.0, 0.0, 1.0, -1.0)):
+            pred[i] = v
+    pred = torch.from_numpy(pred)
+    ga, gb = rnd((numel,), numel + 1), rnd((numel,), numel + 2, 3.0)
+    ga, gb = (ga if which != "b_only" else None), (gb if which != "a_only" else None)
+    want = sum(g.double() for g in (ga, gb) if g is not None) * (1 - pred.double() ** 2)
+    guard = 64
+    dh = torch.full((numel + guard,), float("nan"), dtype=dtype, device=dev())
+    P = pred.to(dev())
+    ops.tanh_bwd(dtype, P, None if ga is None else ga.to(dev()), None if gb is None else gb.to(dev()), dh[:numel])
+    torch.cuda.synchronize()
+    assert torch.isnan(dh[numel:]).all(), "wrote past numel"
+    got = dh[:numel].double().cpu()
+    assert torch.isfinite(got).all()
+    assert torch.equal(got[pred.abs() == 1], torch.zeros(int((pred.abs() == 1).sum()), dtype=torch.float64))
+    scale = float(want.abs().max())
+    print("tanh_bwd", dtype, numel, which, "max_err", max_err(got, want))
+    if dtype == torch.float32:
+        assert max_err(got, want) < 1e-6
+    else:
+        assert bool(((got - want).abs() <= 2.0 ** -8 * want.abs() + 1e-6 * scale).all())
 
 
 def test_adam_matches_torch(pai):

@@ -55,7 +55,7 @@ def _check(PF, pred, target, denorm):
     """pred / target: host tensors as they go INTO eval_images; returns nothing, asserts everything."""
     shape = tuple(pred.shape)
     n, c, h, w = shape
-    strips = STRIPS[shape]
+    strips = STRIPS.get(shape, 0)        # other callers' shapes (tests/test_gpu_ssim_paths.py): whole images only
     dp, dt = (oracle.denormalize(pred), oracle.denormalize(target)) if denorm else (pred, target)
     P, T = pred.to(dev()), target.to(dev())
     res = PF.eval_images(P, T, denorm=denorm, strips=strips, ssim_map=True, hot=True)

@@ -715,8 +715,13 @@ class UnetEngine:
             the alternatives: holding the first decoders' weight gradients back until the main stream is in the bottleneck
             chain, 6.34-6.48 against 6.25-6.27 ms/step; two workgroups per CU for the last one of a pass, no change.)"""
             def run():
-                fn = ops.conv_wgrad if min(_cin_cout(conv)) <= 2 else conv_wgrad
+                thin = min(_cin_cout(conv)) <= 2
+                fn = ops.conv_wgrad if thin else conv_wgrad
                 fn(d, x1, x2, dz, A.seg(conv.weight), A.seg(conv.bias) if with_bias else None)
+                if thin:
+                    # here, not after wgrad() returns: a held launch is issued by flush_held() later, and the event has to
+                    # sit BEHIND the thin kernel on the side stream (which a first pass creates only in the fork around run())
+                    side.mark_scratch()
                 done(conv.bias)
             if batch_n > 1 and dz.numel() // max(1, conv.weight.shape[1] if isinstance(conv, nn.ConvTranspose2d) else conv.weight.shape[0]) <= int(os.environ.get("PAI_WGRAD_BATCH_PIX", "1024")):
                 held.append(run)
@@ -734,8 +739,7 @@ class UnetEngine:
         d = P["dec_desc"][j]
         x1 = S["r"][j - 1]
         x2 = S["z"][0]
-        wgrad(d, x1, x2, dh, self.dec_conv[j], True)
-        side.mark_scratch()
+        wgrad(d, x1, x2, dh, self.dec_conv[j], True)      # thin: its run() marks the scratch event for fork_tail()
         _, wd = self.dec_packs[j].get(dtype)
         part = P["bwd_partials"]
         # Every input-gradient launch also runs the first half of the backward of the layer that PRODUCED its input
