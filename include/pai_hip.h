@@ -135,7 +135,13 @@ int pai_conv_kernel_id(const pai_conv_desc* d, int op);
 /* Symbol (as rocprofv3 --kernel-trace prints it, without "void " and the argument list) of the main
  * kernel such a call launches, e.g. "gg_fwd_patch_k<256, 128, true>"; bench.py keys its per-kernel
  * roofline on it so that the figure can be checked against profiles/ *_kernel_stats.csv.
- * Families without a single dominant kernel report their family name.  Returns 0, < 0 on error. */
+ * The name is a field of the same selection the launch switches on (pick_fwd / pick_wgrad in api.hip), for the
+ * stand-in arguments of a plain call: a raw output per destination tensor, no statistics, no fused epilogue, no bias
+ * gradient.  What it is: the symbol, for the matrix-core tile / patch kernels (ids 2, 3) and, up to its first two template
+ * arguments ("pwx_k<64, 128>": the layer's channel counts), for pwx_k (id 7).  What it is not: the other families report
+ * a family label ("gg_simt", "gg_rowdot", "thin_mfma_bf16", "small_mfma_bf16", "grouped3_k", "grouped3_wgrad_k"), and
+ * for gg_wgrad_patch3_k the trailing ", 0" of the non-pipelined form, which is what launches when the call takes a bias
+ * gradient, is not reported.  Returns 0, < 0 on error. */
 int pai_conv_kernel_name(const pai_conv_desc* d, int op, char* name, int name_len);
 
 /* ---------------------------------------------------------------------------

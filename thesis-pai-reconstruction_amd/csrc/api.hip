@@ -86,6 +86,23 @@ extern "C" int pai_set_tunable(const char* name, int value) {
     return 0;
 }
 
+// Environment switches of the selection code.  The rule: read ONCE per process (every script sets them before it starts),
+// so that a launcher and the query that reports on it cannot see two values.
+int env_int(const char* name, int def) {
+    static struct { const char* name; int value; } seen[16];
+    static int nseen = 0;
+    for (int i = 0; i < nseen; ++i)
+        if (!strcmp(seen[i].name, name)) return seen[i].value;
+    const char* e = getenv(name);
+    const int v = e ? atoi(e) : def;
+    if (nseen < 16) {
+        seen[nseen].name = name;     // (callers pass string literals)
+        seen[nseen].value = v;
+        ++nseen;                     // (published last, as the tunables above)
+    }
+    return v;
+}
+
 static void finish_gg(GG* g);
 
 // ---------------------------------------------------------------------------------
@@ -392,114 +409,174 @@ extern "C" int pai_set_wgrad_workspace(void* device_memory, int64_t bytes) {
     return pai_handle_set_wgrad_workspace(h, device_memory, bytes);
 }
 
+// ---- kernel selection ------------------------------------------------------------------------------------------
+// Which kernel a convolution-family call runs is decided in ONE place per direction -- pick_fwd (forward and input
+// gradient) and pick_wgrad -- and everything the library reports or sizes from that decision is a field of the pick:
+// run_fwd / conv_wgrad_impl switch on `k`, the (descriptor, op) queries read the fields of a pick for stand-in arguments.
+// The branches of the forward chain in the order they are tried, with the public family id (pai_conv_kernel_id) and the
+// reported name of each: a family label, except for the matrix-core and pwx_k families, which report their symbol.
+enum FwdKernel { FK_GROUPED3, FK_PW, FK_THIN_FWD, FK_HEAD_DGRAD, FK_THIN_DGRAD, FK_ROWDOT, FK_PWX, FK_MFMA, FK_SMALL, FK_SIMT,
+                 FK_NONE };       // FK_NONE: a prologue that no kernel of this layer applies
+static const struct { int id; const char* name; } fwd_family[FK_NONE + 1] = {
+    {6, "grouped3_k"}, {4, "thin_mfma_bf16"}, {4, "thin_mfma_bf16"}, {4, "thin_mfma_bf16"}, {4, "thin_mfma_bf16"},
+    {1, "gg_rowdot"}, {7, nullptr /* pwx_kernel_name */}, {2, nullptr /* 2 / 3 by tile width, MfmaPlan::name */},
+    {5, "small_mfma_bf16"}, {0, "gg_simt"}, {-1, ""}};
+
+struct FwdPick {
+    FwdKernel k;
+    int id;                     // pai_conv_kernel_id
+    const char* name;           // pai_conv_kernel_name
+    int rows;                   // BatchNorm statistics rows (a.stats) or producer-backward partial rows (a.bpart) of the launch
+    bool fused;                 // the backward of the producing layer can ride on this launch's store (pai_conv_dgrad_act / _bn)
+    int64_t workspace_bytes;    // to register before the call: split-K slabs of the matrix-core kernel (whenever the layer is
+    int64_t scratch_bytes;      // eligible for it: tunables may move it there) / skinny-GEMM output of the thin input gradient
+    MfmaPlan mfma;              // valid when the layer is eligible for the matrix-core tile kernels
+};
+
+static FwdPick pick_fwd(int dtype, const GG& g, const FwdArgs& a) {
+    FwdPick p = {};
+    const bool mfma = fwd_mfma_ok(dtype, g, a);
+    if (mfma) p.mfma = fwd_mfma_plan(g);
+    if (a.pscale)                     // prologue on x1: only the kernels that apply it on load
+        p.k = grouped3_ok(dtype, g, a) ? FK_GROUPED3 : (pwx_ok(dtype, g, a) ? FK_PWX : FK_NONE);
+    else if (grouped3_ok(dtype, g, a)) p.k = FK_GROUPED3;     // grouped 3x3: 16-channel slices, patch in LDS
+    else if (pw_ok(dtype, g, a)) p.k = FK_PW;
+    else if (thin_fwd_ok(dtype, g, a)) p.k = FK_THIN_FWD;
+    else if (head_dgrad_ok(dtype, g, a)) p.k = FK_HEAD_DGRAD;
+    else if (thin_dgrad_ok(dtype, g, a)) p.k = FK_THIN_DGRAD;
+    else if (fwd_rowdot_ok(g, a)) p.k = FK_ROWDOT;
+    else if (pwx_ok(dtype, g, a)) p.k = FK_PWX;               // big pointwise layers: streaming kernel
+    else if (mfma) p.k = FK_MFMA;
+    else if (small_ok(dtype, g, a)) p.k = FK_SMALL;
+    else p.k = FK_SIMT;
+    p.id = p.k == FK_MFMA && p.mfma.bn != 128 ? 3 : fwd_family[p.k].id;
+    p.name = p.k == FK_MFMA ? p.mfma.name : (p.k == FK_PWX ? pwx_kernel_name(g) : fwd_family[p.k].name);
+    switch (p.k) {
+        case FK_GROUPED3: p.rows = grouped3_rows(g); break;
+        case FK_PW: p.rows = pw_rows(g); break;
+        case FK_PWX: p.rows = pwx_rows(g); break;
+        case FK_MFMA: p.rows = p.mfma.rows * g.nphase; break;
+        case FK_SMALL: p.rows = small_rows(g); break;
+        case FK_SIMT: p.rows = fwd_simt_mtiles(g) * g.nphase; break;
+        default: p.rows = 0; break;     // (the thin and row-dot kernels take no statistics)
+    }
+    // the tile kernels, pw_k and pwx_k have the fused store; a pointwise layer picked here for pwx_k goes to whichever of
+    // pwx_k and the tile kernel takes the epilogue asked for, once its fields are set
+    p.fused = p.k == FK_PW || (mfma && (p.k == FK_PWX || p.k == FK_MFMA));
+    p.workspace_bytes = mfma ? p.mfma.workspace_bytes : 0;
+    p.scratch_bytes = thin_dgrad_shape_ok(dtype, g) ? thin_dgrad_scratch_bytes(g, a) : 0;
+    return p;
+}
+
+static int run_fwd(const FwdPick& p, int dtype, const GG& g, const FwdArgs& a, hipStream_t s) {
+    switch (p.k) {
+        case FK_GROUPED3: return launch_grouped3(g, a, s);
+        case FK_PW: return launch_pw(g, a, s);
+        case FK_THIN_FWD: return launch_thin_fwd(g, a, s);
+        case FK_HEAD_DGRAD: return launch_head_dgrad(g, a, s);
+        case FK_THIN_DGRAD: return launch_thin_dgrad(g, a, s);
+        case FK_ROWDOT: return launch_fwd_rowdot(dtype, g, a, s);
+        case FK_PWX: return launch_pwx(g, a, s);
+        case FK_MFMA: return launch_fwd_mfma(g, a, p.mfma, s);
+        case FK_SMALL: return launch_small(g, a, s);
+        case FK_SIMT: return launch_fwd_simt(dtype, g, a, s);
+        case FK_NONE: break;
+    }
+    pai_set_error("pai_conv_fwd_pro: this layer takes no prologue (ask pai_conv_prologue_ok)");
+    return 1;
+}
+static int run_fwd(int dtype, const GG& g, const FwdArgs& a, hipStream_t s) { return run_fwd(pick_fwd(dtype, g, a), dtype, g, a, s); }
+
+// The weight-gradient chain in the order it is tried.
+enum WgradKernel { WK_GROUPED3, WK_THIN_CONV, WK_THIN_CONVT, WK_THIN_CONV1, WK_THIN_CONV3, WK_THIN_CONV3T, WK_ROWDOT, WK_MFMA,
+                   WK_SIMT, WK_NONE };   // WK_NONE: a prologue this layer's weight gradient cannot apply
+static const struct { int id; const char* name; } wgrad_family[WK_NONE + 1] = {
+    {6, "grouped3_wgrad_k"}, {4, "thin_mfma_bf16"}, {4, "thin_mfma_bf16"}, {4, "thin_mfma_bf16"}, {4, "thin_mfma_bf16"},
+    {4, "thin_mfma_bf16"}, {1, "gg_rowdot"}, {2, nullptr /* 2 / 3 by Cout % 128, MfmaPlan::name */}, {0, "gg_simt"}, {-1, ""}};
+
+struct WgradPick {
+    WgradKernel k;
+    int id;
+    const char* name;
+    bool overwrites;            // an overwriting call needs no clear of dw first: every element has one writer
+    float* part;                // WK_GROUPED3: the registered weight-gradient workspace
+    int64_t workspace_bytes;    // weight-gradient workspace to register (grouped 3 x 3 partial blocks / pixel-split slabs)
+    int64_t scratch_bytes;      // partial tiles of the thin forms
+    MfmaPlan mfma;              // valid when wgrad_mfma_ok
+};
+
+static WgradPick pick_wgrad(int dtype, const GG& g, bool has_dbias, bool has_prologue) {
+    WgradPick p = {};
+    const bool grouped = grouped3_wgrad_ok(dtype, g, has_dbias ? (const float*)1 : nullptr), mfma = wgrad_mfma_ok(dtype, g);
+    if (mfma) p.mfma = wgrad_mfma_plan(g, has_dbias, has_prologue);
+    p.part = grouped ? wgrad_slab_acquire(grouped3_wgrad_part_bytes(g)) : nullptr;
+    const WgradKernel thin = thin_wgrad_conv_ok(dtype, g) ? WK_THIN_CONV : thin_wgrad_convt_ok(dtype, g) ? WK_THIN_CONVT
+                           : thin_wgrad_conv1_ok(dtype, g) ? WK_THIN_CONV1 : thin_wgrad_conv3_ok(dtype, g) ? WK_THIN_CONV3
+                           : thin_wgrad_conv3t_ok(dtype, g) ? WK_THIN_CONV3T : WK_NONE;
+    const int chunks = g.Cin / 8;       // row-dot: one or two filters, the channel chunks a power of two up to 256
+    const bool rowdot = g.Cout <= 2 && (g.ntaps == 4 || g.ntaps == 9 || g.ntaps == 16) && (g.C1 % 8) == 0 && (g.C2 % 8) == 0 &&
+                        chunks <= 256 && (chunks & (chunks - 1)) == 0;
+    // through a prologue: the grouped 3 x 3 kernel with its workspace registered, or the pointwise tile kernel
+    if (has_prologue) p.k = grouped ? (p.part ? WK_GROUPED3 : WK_NONE) : (wgrad_pro_ok(dtype, g) ? WK_MFMA : WK_NONE);
+    else if (p.part) p.k = WK_GROUPED3;     // block-diagonal 3 x 3 filter: the diagonal blocks only (gg_group.hip)
+    else if (thin != WK_NONE) p.k = thin;
+    else if (rowdot) p.k = WK_ROWDOT;
+    else p.k = mfma ? WK_MFMA : WK_SIMT;
+    p.id = p.k == WK_MFMA && (g.Cout % 128) != 0 ? 3 : wgrad_family[p.k].id;
+    p.name = p.k == WK_MFMA ? p.mfma.name : wgrad_family[p.k].name;
+    p.overwrites = p.k == WK_GROUPED3 || (p.k == WK_MFMA && p.mfma.overwrites);
+    p.workspace_bytes = grouped ? grouped3_wgrad_part_bytes(g) : (mfma ? p.mfma.workspace_bytes : 0);
+    p.scratch_bytes = thin == WK_THIN_CONV    ? thin_wgrad_scratch_bytes((int64_t)g.N * g.OHg * g.OWg, g.C1 + g.C2, g.Cout)
+                      : thin == WK_THIN_CONV3 ? thin_wgrad_scratch_bytes((int64_t)g.N * g.OHg * g.OWg, 1, g.Cout)
+                      : thin != WK_NONE       ? thin_wgrad_scratch_bytes((int64_t)g.N * g.H * g.W, 1, g.Cin) : 0;
+    return p;
+}
+
+// stand-in arguments of the (descriptor, op) queries, op 0 / 1: a raw output per destination tensor, nothing else
+static FwdArgs query_args(const GG& g, int op) {
+    FwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y1 = (void*)1;
+    if (op == 1 && g.D2 > 0) a.y2 = (void*)1;
+    return a;
+}
+
 extern "C" int64_t pai_conv_wgrad_workspace_bytes(const pai_conv_desc* d) {
     GG g;
     if (gg_build_fwd(d, &g)) return -1;
-    if (grouped3_wgrad_ok(d->dtype, g, nullptr)) return grouped3_wgrad_part_bytes(g);
-    if (!wgrad_mfma_ok(d->dtype, g)) return 0;
-    return wgrad3_slab_bytes(g);
+    return pick_wgrad(d->dtype, g, false, false).workspace_bytes;
 }
 
 extern "C" int64_t pai_conv_workspace_bytes(const pai_conv_desc* d, int op) {
     GG g;
     if (op == 1 ? gg_build_dgrad(d, &g) : gg_build_fwd(d, &g)) return -1;
-    if (op == 2) return 0;
-    FwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y1 = (void*)1;
-    if (op == 1) a.y2 = (void*)1;
-    if (!fwd_mfma_ok(d->dtype, g, a)) return 0;
-    return fwd_mfma_workspace_bytes(g);
+    return op == 2 ? 0 : pick_fwd(d->dtype, g, query_args(g, op)).workspace_bytes;
 }
 
 extern "C" int64_t pai_conv_scratch_bytes(const pai_conv_desc* d, int op) {
     GG g;
     if (op == 1 ? gg_build_dgrad(d, &g) : gg_build_fwd(d, &g)) return -1;
-    if (op == 2) {
-        if (thin_wgrad_conv_ok(d->dtype, g)) return thin_wgrad_scratch_bytes((int64_t)g.N * g.OHg * g.OWg, g.C1 + g.C2, g.Cout);
-        if (thin_wgrad_convt_ok(d->dtype, g) || thin_wgrad_conv1_ok(d->dtype, g) || thin_wgrad_conv3t_ok(d->dtype, g))
-            return thin_wgrad_scratch_bytes((int64_t)g.N * g.H * g.W, 1, g.Cin);
-        if (thin_wgrad_conv3_ok(d->dtype, g)) return thin_wgrad_scratch_bytes((int64_t)g.N * g.OHg * g.OWg, 1, g.Cout);
-        return 0;
-    }
-    FwdArgs a;
-    memset(&a, 0, sizeof(a));
-    if (thin_dgrad_shape_ok(d->dtype, g)) return thin_dgrad_scratch_bytes(g, a);
-    return 0;
+    return op == 2 ? pick_wgrad(d->dtype, g, false, false).scratch_bytes : pick_fwd(d->dtype, g, query_args(g, op)).scratch_bytes;
 }
-
-// ---------------------------------------------------------------------------------
-static bool use_mfma(int dtype, const GG& g, const FwdArgs& a) { return fwd_mfma_ok(dtype, g, a); }
 
 extern "C" int pai_conv_fwd_stats_rows(const pai_conv_desc* d) {
     GG g;
     if (gg_build_fwd(d, &g)) return -1;
-    FwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y1 = (void*)1;  // raw output present
+    FwdArgs a = query_args(g, 0);
     a.stats = (float*)1;
-    if (grouped3_ok(d->dtype, g, a)) return grouped3_rows(g);
-    if (pw_ok(d->dtype, g, a)) return pw_rows(g);
-    if (pwx_ok(d->dtype, g, a)) return pwx_rows(g);
-    if (!thin_fwd_ok(d->dtype, g, a) && !fwd_rowdot_ok(g, a) && !use_mfma(d->dtype, g, a) && small_ok(d->dtype, g, a))
-        return small_rows(g);
-    int mt = use_mfma(d->dtype, g, a) ? fwd_mfma_mtiles(g) : fwd_simt_mtiles(g);
-    return mt * g.nphase;
+    return pick_fwd(d->dtype, g, a).rows;
 }
 
 extern "C" int pai_conv_kernel_id(const pai_conv_desc* d, int op) {
     GG g;
-    FwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y1 = (void*)1;
-    if (op == 1) {
-        if (gg_build_dgrad(d, &g)) return -1;
-        a.y2 = (void*)1;
-    } else {
-        if (gg_build_fwd(d, &g)) return -1;
-    }
-    if (op == 2) {
-        if (grouped3_wgrad_ok(d->dtype, g, nullptr) && wgrad_slab_acquire(grouped3_wgrad_part_bytes(g))) return 6;
-        if (thin_wgrad_conv_ok(d->dtype, g) || thin_wgrad_convt_ok(d->dtype, g) || thin_wgrad_conv1_ok(d->dtype, g) ||
-            thin_wgrad_conv3_ok(d->dtype, g) || thin_wgrad_conv3t_ok(d->dtype, g)) return 4;
-        if (g.Cout <= 2 && (g.ntaps == 4 || g.ntaps == 9 || g.ntaps == 16) && (g.C1 % 8) == 0 && (g.C2 % 8) == 0) {
-            int chunks = g.Cin / 8;
-            if (chunks <= 256 && (chunks & (chunks - 1)) == 0) return 1;
-        }
-        if (wgrad_mfma_ok(d->dtype, g)) return (g.Cout % 128) == 0 ? 2 : 3;
-        return 0;
-    }
-    if (op != 2 && grouped3_ok(d->dtype, g, a)) return 6;
-    if (thin_fwd_ok(d->dtype, g, a) || thin_dgrad_ok(d->dtype, g, a) || pw_ok(d->dtype, g, a)) return 4;
-    if (op == 1 && g.D2 == 0) {          // single-destination input gradients: the PatchGAN head's own kernel
-        FwdArgs a1 = a;
-        a1.y2 = nullptr;
-        if (head_dgrad_ok(d->dtype, g, a1)) return 4;
-    }
-    if (fwd_rowdot_ok(g, a)) return 1;
-    if (pwx_ok(d->dtype, g, a)) return 7;
-    if (fwd_mfma_ok(d->dtype, g, a))
-        return ((g.Cout % 128) == 0 && (g.D2 == 0 || (g.D1 % 128) == 0)) ? 2 : 3;
-    if (small_ok(d->dtype, g, a)) return 5;
-    return 0;
+    if (op == 1 ? gg_build_dgrad(d, &g) : gg_build_fwd(d, &g)) return -1;
+    return op == 2 ? pick_wgrad(d->dtype, g, false, false).id : pick_fwd(d->dtype, g, query_args(g, op)).id;
 }
 
 extern "C" int pai_conv_kernel_name(const pai_conv_desc* d, int op, char* name, int name_len) {
-    static const char* fam[8] = {"gg_simt", "gg_rowdot", "gg_mfma", "gg_mfma", "thin_mfma_bf16", "small_mfma_bf16", "grouped3_k",
-                                 "pwx_k"};
-    const int id = pai_conv_kernel_id(d, op);
-    if (id < 0 || !name || name_len <= 0) return -1;
-    const char* n = (id == 6 && op == 2) ? "grouped3_wgrad_k" : fam[id];
-    if (id == 2 || id == 3) {
-        GG g;
-        if (op == 1 ? gg_build_dgrad(d, &g) : gg_build_fwd(d, &g)) return -1;
-        n = op == 2 ? wgrad_mfma_kernel_name(g) : fwd_mfma_kernel_name(g);
-    }
-    if (id == 7) {
-        GG g;
-        if (op == 1 ? gg_build_dgrad(d, &g) : gg_build_fwd(d, &g)) return -1;
-        n = pwx_kernel_name(g);
-    }
+    GG g;
+    if ((op == 1 ? gg_build_dgrad(d, &g) : gg_build_fwd(d, &g)) || !name || name_len <= 0) return -1;
+    const char* n = op == 2 ? pick_wgrad(d->dtype, g, false, false).name : pick_fwd(d->dtype, g, query_args(g, op)).name;
     strncpy(name, n, name_len - 1);
     name[name_len - 1] = 0;
     return 0;
@@ -511,25 +588,6 @@ extern "C" int pai_conv_fwd_stats_rows_max(const pai_conv_desc* d) {
     GG g;
     if (gg_build_fwd(d, &g)) return -1;
     return cdiv(g.M, 16) * g.nphase;
-}
-
-static int run_fwd(int dtype, const GG& g, const FwdArgs& a, hipStream_t s) {
-    if (a.pscale) {                     // prologue on x1: only the kernels that apply it on load
-        if (grouped3_ok(dtype, g, a)) return launch_grouped3(g, a, s);
-        if (pwx_ok(dtype, g, a)) return launch_pwx(g, a, s);
-        pai_set_error("pai_conv_fwd_pro: this layer takes no prologue (ask pai_conv_prologue_ok)");
-        return 1;
-    }
-    if (grouped3_ok(dtype, g, a)) return launch_grouped3(g, a, s);   // grouped 3x3: 16-channel slices, patch in LDS
-    if (pw_ok(dtype, g, a)) return launch_pw(g, a, s);
-    if (thin_fwd_ok(dtype, g, a)) return launch_thin_fwd(g, a, s);
-    if (head_dgrad_ok(dtype, g, a)) return launch_head_dgrad(g, a, s);
-    if (thin_dgrad_ok(dtype, g, a)) return launch_thin_dgrad(g, a, s);
-    if (fwd_rowdot_ok(g, a)) return launch_fwd_rowdot(dtype, g, a, s);
-    if (pwx_ok(dtype, g, a)) return launch_pwx(g, a, s);             // big pointwise layers: streaming kernel
-    if (use_mfma(dtype, g, a)) return launch_fwd_mfma(g, a, s);
-    if (small_ok(dtype, g, a)) return launch_small(g, a, s);
-    return launch_fwd_simt(dtype, g, a, s);
 }
 
 extern "C" int pai_conv_fwd(const pai_conv_desc* d, const void* x1, const void* x2,
@@ -555,25 +613,13 @@ static int conv_wgrad_impl(const pai_conv_desc* d, const void* x1, const void* x
 // ---- prologue: the input read as act(x * scale[c] + shift[c]) -- the BatchNorm + activation of the producing layer applied
 // on load, so that its activated tensor is never written (reference models/res_unet.py:143-147: Conv2d -> BatchNorm2d -> ReLU ->
 // Conv2d; the second convolution and its weight gradient read the first one's raw output)
-static bool prologue_fwd_ok(const pai_conv_desc* d, const GG& g) {
-    FwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y1 = (void*)1;
-    a.pscale = a.pshift = (const float*)1;
-    a.pact = PAI_ACT_RELU;
-    return grouped3_ok(d->dtype, g, a) || pwx_ok(d->dtype, g, a);
-}
-
-// weight gradient through a prologue: the pointwise tile kernel, or the grouped 3 x 3 kernel with its workspace registered
-static bool prologue_wgrad_ok(const pai_conv_desc* d, const GG& g) {
-    if (grouped3_wgrad_ok(d->dtype, g, nullptr)) return wgrad_slab_acquire(grouped3_wgrad_part_bytes(g)) != nullptr;
-    return wgrad_pro_ok(d->dtype, g);
-}
-
 extern "C" int pai_conv_prologue_ok(const pai_conv_desc* d) {
     GG g;
     if (gg_build_fwd(d, &g)) return 0;
-    return prologue_fwd_ok(d, g) && prologue_wgrad_ok(d, g);
+    FwdArgs a = query_args(g, 0);
+    a.pscale = a.pshift = (const float*)1;
+    a.pact = PAI_ACT_RELU;
+    return pick_fwd(d->dtype, g, a).k != FK_NONE && pick_wgrad(d->dtype, g, false, true).k != WK_NONE;
 }
 
 extern "C" int pai_conv_fwd_pro(const pai_conv_desc* d, const void* x1, const void* w_fwd, const float* bias, void* y_raw,
@@ -615,13 +661,6 @@ extern "C" int pai_conv_dgrad(const pai_conv_desc* d, const void* dy, const void
     return run_fwd(d->dtype, g, a, (hipStream_t)stream);
 }
 
-static bool dgrad_store_fusable(const pai_conv_desc* d, const GG& g, const FwdArgs& a) {
-    if (grouped3_ok(d->dtype, g, a)) return false;
-    if (pw_ok(d->dtype, g, a)) return true;
-    return !thin_fwd_ok(d->dtype, g, a) && !thin_dgrad_ok(d->dtype, g, a) && !fwd_rowdot_ok(g, a) &&
-           use_mfma(d->dtype, g, a);
-}
-
 extern "C" int pai_conv_dgrad_act(const pai_conv_desc* d, const void* dy, const void* w_dgrad,
                                   void* dx1, void* dx2, const void* a1, int act1, void* stream) {
     GG g;
@@ -635,9 +674,13 @@ extern "C" int pai_conv_dgrad_act(const pai_conv_desc* d, const void* dy, const 
     a.y1 = dx1; a.y2 = dx2;
     hipStream_t s = (hipStream_t)stream;
     // (the PatchGAN head's own kernel applies the activation derivative in its store too: nothing else is asked of it here)
-    const bool fused = dgrad_store_fusable(d, g, a) || (!thin_fwd_ok(d->dtype, g, a) && head_dgrad_ok(d->dtype, g, a));
-    if (fused) { a.bz = a1; a.bact1 = act1; }
-    int rc = run_fwd(d->dtype, g, a, s);
+    FwdPick p = pick_fwd(d->dtype, g, a);
+    const bool fused = p.fused || p.k == FK_HEAD_DGRAD;
+    if (fused) {                // (picked again: the epilogue asked for decides between pwx_k and the tile kernel)
+        a.bz = a1; a.bact1 = act1;
+        p = pick_fwd(d->dtype, g, a);
+    }
+    int rc = run_fwd(p, d->dtype, g, a, s);
     if (rc || fused || act1 == PAI_ACT_NONE) return rc;
     // kernels without the fused store: the same product as a second pass, in place
     return pai_act_bwd(d->dtype, dx1, act1, nullptr, PAI_ACT_NONE, a1, (int64_t)g.N * g.OH * g.OW * g.D1, dx1, stream);
@@ -673,15 +716,16 @@ extern "C" int pai_conv_dgrad_bn(const pai_conv_desc* d, const void* dy, const v
     a.y1 = dx1; a.y2 = dx2;
     hipStream_t s = (hipStream_t)stream;
     const int64_t M = (int64_t)g.N * g.OH * g.OW;
-    if (dgrad_store_fusable(d, g, a)) {
+    const FwdPick plain = pick_fwd(d->dtype, g, a);
+    if (plain.fused) {
         a.bz = e->z; a.badd = e->add;
         a.bscale = e->scale; a.bshift = e->shift; a.bmean = e->mean; a.brstd = e->rstd;
         a.bact1 = e->act1; a.bact2 = e->act2;
         a.bpart = e->partials;
-        if (partial_rows)
-            *partial_rows = !e->partials ? 0 : (pw_ok(d->dtype, g, a) ? pw_rows(g) : pwx_ok(d->dtype, g, a) ? pwx_rows(g)
-                                                                                      : fwd_mfma_mtiles(g) * g.nphase);
-        return run_fwd(d->dtype, g, a, s);
+        const FwdPick p = pick_fwd(d->dtype, g, a);     // pwx_k or the tile kernel, by the epilogue asked for
+        PAI_CHECK(p.fused, "pai_conv_dgrad_bn: no kernel with the fused store takes this epilogue");
+        if (partial_rows) *partial_rows = e->partials ? p.rows : 0;
+        return run_fwd(p, d->dtype, g, a, s);
     }
     if (e->partials) {
         // thin -> wide input gradient (the head of the U-Net): the pass rides on thin_fwd2_k's store
@@ -692,7 +736,7 @@ extern "C" int pai_conv_dgrad_bn(const pai_conv_desc* d, const void* dy, const v
         }
     }
     // other kernel families: plain input gradient, then the same arithmetic as a second pass in place
-    int rc = run_fwd(d->dtype, g, a, s);
+    int rc = run_fwd(plain, d->dtype, g, a, s);
     if (rc) return rc;
     if (e->partials) {
         *partial_rows = pai_bn_bwd_partial_rows(M);
@@ -721,8 +765,9 @@ extern "C" int pai_conv_fwd_bn(const pai_conv_desc* d, const void* x1, const voi
     a.eact = PAI_ACT_NONE;
     hipStream_t s = (hipStream_t)stream;
     const int64_t count = (int64_t)g.N * g.OH * g.OW;
-    if (int rc = run_fwd(d->dtype, g, a, s)) return rc;
-    const int rows = pai_conv_fwd_stats_rows(d);
+    const FwdPick p = pick_fwd(d->dtype, g, a);
+    if (int rc = run_fwd(p, d->dtype, g, a, s)) return rc;
+    const int rows = p.rows;
     if (bn_fuse_small_ok(rows, count, g.Cout))      // the U-Net bottleneck: finalize + apply as ONE launch, same results
         return launch_bn_fin_apply(d->dtype, stats, rows, g.Cout, count, bn->gamma, bn->beta, bn->eps, bn->momentum,
                                    bn->n_updates, bn->running_mean, bn->running_var, bn->num_batches_tracked, bn->mean,
@@ -796,60 +841,29 @@ static int conv_wgrad_impl(const pai_conv_desc* d, const void* x1, const void* x
     a.x1 = x1; a.x2 = x2; a.dy = dy; a.dw = dw; a.dbias = dbias; a.overwrite = 0; a.overwrite_bias = 0; a.slab = nullptr;
     a.pscale = pscale; a.pshift = pshift; a.pact = pact;
     hipStream_t s = (hipStream_t)stream;
-    if (pscale && grouped3_wgrad_ok(d->dtype, g, dbias)) {
-        float* part = wgrad_slab_acquire(grouped3_wgrad_part_bytes(g));
-        PAI_CHECK(part, "pai_conv_wgrad_pro: the grouped 3 x 3 weight gradient needs its workspace (pai_set_wgrad_workspace)");
-        a.overwrite = overwrite != 0;
-        return launch_grouped3_wgrad(g, a, part, s);
-    }
-    if (pscale) {
-        PAI_CHECK(wgrad_pro_ok(d->dtype, g), "pai_conv_wgrad_pro: this layer takes no prologue (ask pai_conv_prologue_ok)");
-        if (overwrite && wgrad_mfma_can_overwrite(g)) {
-            a.overwrite = 1;
-            a.overwrite_bias = overwrite == 1;
-        } else if (overwrite) {
-            hipError_t e = pai::memset_async(dw, 0, (size_t)g.Cout * g.wtaps * g.Cin * sizeof(float), s);
-            PAI_CHECK(e == hipSuccess, "pai_conv_wgrad_pro: hipMemsetAsync: %s", hipGetErrorString(e));
-            if (dbias && overwrite == 1) {
-                e = pai::memset_async(dbias, 0, (size_t)g.Cout * sizeof(float), s);
-                PAI_CHECK(e == hipSuccess, "pai_conv_wgrad_pro: hipMemsetAsync: %s", hipGetErrorString(e));
-            }
-        }
-        return launch_wgrad_mfma(g, a, s);
-    }
-    if (grouped3_wgrad_ok(d->dtype, g, dbias)) {      // block-diagonal 3 x 3 filter: the diagonal blocks only (gg_group.hip)
-        float* part = wgrad_slab_acquire(grouped3_wgrad_part_bytes(g));
-        if (part) {
-            a.overwrite = overwrite != 0;
-            return launch_grouped3_wgrad(g, a, part, s);
-        }
-    }
-    if (overwrite) {
-        const bool thin = thin_wgrad_conv_ok(d->dtype, g) || thin_wgrad_convt_ok(d->dtype, g) ||
-                          thin_wgrad_conv1_ok(d->dtype, g) || thin_wgrad_conv3_ok(d->dtype, g) ||
-                          thin_wgrad_conv3t_ok(d->dtype, g);
-        const bool rowdot = g.Cout <= 2 && (g.ntaps == 4 || g.ntaps == 9 || g.ntaps == 16) && (g.C1 % 8) == 0 && (g.C2 % 8) == 0;
-        if (!thin && !rowdot && wgrad_mfma_ok(d->dtype, g) && wgrad_mfma_can_overwrite(g)) {
-            a.overwrite = 1;       // every element has exactly one writer: plain stores, nothing to clear
-            a.overwrite_bias = overwrite == 1;
-        } else {                   // the accumulating kernels: clear first
-            hipError_t e = pai::memset_async(dw, 0, (size_t)g.Cout * g.wtaps * g.Cin * sizeof(float), s);
+    const WgradPick p = pick_wgrad(d->dtype, g, dbias != nullptr, pscale != nullptr);
+    PAI_CHECK(p.k != WK_NONE, "pai_conv_wgrad_pro: this layer takes no prologue (ask pai_conv_prologue_ok: the grouped 3 x 3 weight "
+                              "gradient needs its workspace, pai_set_wgrad_workspace)");
+    if (overwrite && p.overwrites) {
+        a.overwrite = 1;           // every element has exactly one writer: plain stores, nothing to clear
+        a.overwrite_bias = p.k != WK_GROUPED3 && overwrite == 1;
+    } else if (overwrite) {        // the accumulating kernels: clear first
+        hipError_t e = pai::memset_async(dw, 0, (size_t)g.Cout * g.wtaps * g.Cin * sizeof(float), s);
+        PAI_CHECK(e == hipSuccess, "pai_conv_wgrad_overwrite: hipMemsetAsync: %s", hipGetErrorString(e));
+        if (dbias && overwrite == 1) {
+            e = pai::memset_async(dbias, 0, (size_t)g.Cout * sizeof(float), s);
             PAI_CHECK(e == hipSuccess, "pai_conv_wgrad_overwrite: hipMemsetAsync: %s", hipGetErrorString(e));
-            if (dbias && overwrite == 1) {
-                e = pai::memset_async(dbias, 0, (size_t)g.Cout * sizeof(float), s);
-                PAI_CHECK(e == hipSuccess, "pai_conv_wgrad_overwrite: hipMemsetAsync: %s", hipGetErrorString(e));
-            }
         }
     }
-    if (thin_wgrad_conv_ok(d->dtype, g)) return launch_thin_wgrad_conv(g, a, s);
-    if (thin_wgrad_convt_ok(d->dtype, g)) return launch_thin_wgrad_convt(g, a, s);
-    if (thin_wgrad_conv1_ok(d->dtype, g)) return launch_thin_wgrad_conv1(g, a, s);
-    if (thin_wgrad_conv3_ok(d->dtype, g)) return launch_thin_wgrad_conv3(g, a, s);
-    if (thin_wgrad_conv3t_ok(d->dtype, g)) return launch_thin_wgrad_conv3t(g, a, s);
-    if (g.Cout <= 2 && (g.ntaps == 4 || g.ntaps == 9 || g.ntaps == 16) && (g.C1 % 8) == 0 && (g.C2 % 8) == 0) {
-        int chunks = g.Cin / 8;
-        if (chunks <= 256 && (chunks & (chunks - 1)) == 0) return launch_wgrad_rowdot(d->dtype, g, a, s);
+    switch (p.k) {
+        case WK_GROUPED3: return launch_grouped3_wgrad(g, a, p.part, s);
+        case WK_THIN_CONV: return launch_thin_wgrad_conv(g, a, s);
+        case WK_THIN_CONVT: return launch_thin_wgrad_convt(g, a, s);
+        case WK_THIN_CONV1: return launch_thin_wgrad_conv1(g, a, s);
+        case WK_THIN_CONV3: return launch_thin_wgrad_conv3(g, a, s);
+        case WK_THIN_CONV3T: return launch_thin_wgrad_conv3t(g, a, s);
+        case WK_ROWDOT: return launch_wgrad_rowdot(d->dtype, g, a, s);
+        case WK_MFMA: return launch_wgrad_mfma(g, a, p.mfma, s);
+        default: return launch_wgrad_simt(d->dtype, g, a, s);
     }
-    if (wgrad_mfma_ok(d->dtype, g)) return launch_wgrad_mfma(g, a, s);
-    return launch_wgrad_simt(d->dtype, g, a, s);
 }

@@ -160,6 +160,18 @@ struct GG {
     int solo;    // pai_conv_desc.hints & PAI_HINT_SOLO: nothing else runs beside this launch (launch geometry only)
 };
 
+// geometry of the patch-resident kernels (patch_geo, gg_tile.h); a kernel argument like GG
+struct PatchGeo {
+    int groups;                    // windows per phase: 1 or 4
+    int TY, TX;                    // 8 x 16 tiles per image
+    signed char by[4][4], bx[4][4];  // [phase][window] source offset of patch pixel (0,0) from (gy0*S, gx0*S)
+    unsigned toff4[4][4];          // 4 x 8 bit: patch offset ty*17+tx of the window's taps
+    unsigned wt4[4][4];            // 4 x 8 bit: weight tap slot of the window's taps
+    // the same per phase, packed for the forward kernel's scalar registers (patch_geo_pack): weight tap slots 4 bits per
+    // (window, tap) -- windows 0-1 in wt_lo, 2-3 in wt_hi -- and patch offsets (ty, tx) 2 bits per (window, tap)
+    unsigned wt_lo[4], wt_hi[4], toff2[4];
+};
+
 // forward gather of a pai_conv_desc (Conv2d or ConvTranspose2d)
 int gg_build_fwd(const pai_conv_desc* d, GG* g);
 // input-gradient gather: source = dy of the layer, destination = dx
@@ -216,17 +228,31 @@ int ew_stream_bn2_bwd_apply(int dtype, const void* d, int act_a, const void* za,
                             const float* scale_a, const float* shift_a, const float* mean_a, const float* rstd_a,
                             const float* gamma_a, const float* sums_a, const float* mean_b, const float* rstd_b,
                             const float* gamma_b, const float* sums_b, void* dza, void* dzb, hipStream_t s);
-int fwd_mfma_ksplit_effective(const GG& g);     // the K split launch_fwd_mfma uses with the registered workspace
 int launch_fwd_simt(int dtype, const GG& g, const FwdArgs& a, hipStream_t s);
 int launch_fwd_rowdot(int dtype, const GG& g, const FwdArgs& a, hipStream_t s);
-int launch_fwd_mfma(const GG& g, const FwdArgs& a, hipStream_t s);
 // run-time tunables (pai_set_tunable): kernel-selection switches for A/B timing and for tests that pin a kernel
 int pai_tunable(const char* name, int def);
-int fwd_mfma_ksplit(const GG& g);
-const char* fwd_mfma_kernel_name(const GG& g);
-const char* wgrad_mfma_kernel_name(const GG& g);
+// environment switch of the selection code (PAI_FWD_MODE, PAI_NO_PATCH, ...): read ONCE per process, set it before the start
+int env_int(const char* name, int def);
+// Selection inside a matrix-core family (gg_mfma.hip, gg_wg3.hip): ONE function decides the variant, its rocprofv3 symbol
+// and the launch geometry; the launcher switches on `variant`, every query (name, rows, bytes) reads a field.
+struct MfmaPlan {
+    int variant;                    // the family's own enum
+    const char* name;
+    int bm, bn, db;                 // tile; db: two LDS stages (tile kernels) / two weight-tile buffers (patch kernels)
+    int ksplit, mtiles, ntiles;     // forward: K splits in use, row / column tiles; weight gradient: pixel splits, co / j tiles
+    int rows;                       // forward: statistics / partial rows per phase; weight gradient: pixels per split
+    unsigned grid, block;
+    size_t lds;
+    int64_t workspace_bytes;        // forward: split-K slabs the cost model asks for; weight gradient: slab of the pixel splits
+    bool overwrites;                // weight gradient: every dW element has one writer (no clear before an overwriting call)
+    PatchGeo pg;
+};
+enum WgradMfmaVariant { WG3_128x64 = 1, WG3_64x128, WG3_128x64_8, WGRAD_PATCH128, WGRAD_PATCH64, WGRAD_TILE128, WGRAD_TILE64 };
+MfmaPlan fwd_mfma_plan(const GG& g);
+int launch_fwd_mfma(const GG& g, const FwdArgs& a, const MfmaPlan& p, hipStream_t s);
+MfmaPlan wgrad_mfma_plan(const GG& g, bool has_dbias, bool has_prologue);
 bool wgrad_pro_ok(int dtype, const GG& g);
-int64_t fwd_mfma_workspace_bytes(const GG& g);
 // Per-device handle (pai_create / pai_bind): owner of the caller-provided split-K workspace and general scratch.
 // Entry points use the ACTIVE handle of the current HIP device (pai_ctx()); there is no process-wide buffer.
 struct pai_handle_s {
@@ -242,7 +268,6 @@ struct pai_handle_s {
 // no workspace, no scratch -> un-split / fallback kernels)
 const pai_handle_s* pai_ctx();
 int fwd_simt_mtiles(const GG& g);
-int fwd_mfma_mtiles(const GG& g);
 bool fwd_mfma_ok(int dtype, const GG& g, const FwdArgs& a);
 // skinny pointwise convolution (64 <-> 32 channels) on the matrix cores, no LDS (gg_mfma.hip)
 bool pw_ok(int dtype, const GG& g, const FwdArgs& a);
@@ -252,7 +277,7 @@ int launch_pw(const GG& g, const FwdArgs& a, hipStream_t s);
 bool pwx_ok(int dtype, const GG& g, const FwdArgs& a);
 int pwx_rows(const GG& g);
 int launch_pwx(const GG& g, const FwdArgs& a, hipStream_t s);
-const char* pwx_kernel_name(const GG& g);
+const char* pwx_kernel_name(const GG& g);     // "pwx_k<Cin, Cout>": the symbol's first two template arguments
 bool fwd_rowdot_ok(const GG& g, const FwdArgs& a);
 // 16- / 32-channel 1x1 and 3x3 convolutions on the matrix cores, no LDS (gg_small.hip)
 bool small_ok(int dtype, const GG& g, const FwdArgs& a);
@@ -279,7 +304,7 @@ struct WgradArgs {
     const void *x1, *x2, *dy;
     float* dw;
     float* dbias;
-    int overwrite;   // dw = instead of +=; honoured by gg_wgrad_mfma_k when wgrad_mfma_can_overwrite(g)
+    int overwrite;   // dw = instead of +=; honoured by the matrix-core kernels when their plan says `overwrites`
     int overwrite_bias;   // dbias = instead of += (pai_conv_wgrad_overwrite; 0 for pai_conv_wgrad_overwrite_w: the caller cleared dbias)
     float* slab;     // set by the launcher: pixel split `s` stores its tile into slab + s * |dW| (plain stores, no atomics)
     // prologue of x1 as in FwdArgs (pai_conv_wgrad_pro): gg_wgrad_mfma_k on pointwise layers, grouped3_wgrad_k
@@ -300,15 +325,11 @@ int launch_eval_planes(const float* pred, const float* target, int NC, int H, in
 const char* eval_planes_kernel_name();
 // patch-resident weight gradient with 128 x 64 / 64 x 128 wave tiles (gg_wg3.hip)
 bool wgrad3_ok(const GG& g);
-int launch_wgrad3(const GG& g, const WgradArgs& a, hipStream_t s);
-const char* wgrad3_kernel_name(const GG& g);
-int64_t wgrad3_slab_bytes(const GG& g);
-bool wgrad3_overwrites(const GG& g);
-// un-split, single-phase launch of gg_wgrad_mfma_k: every dW element has exactly one writer
-bool wgrad_mfma_can_overwrite(const GG& g);
+MfmaPlan wgrad3_plan(const GG& g, bool has_dbias);
+int launch_wgrad3(const GG& g, const WgradArgs& a, const MfmaPlan& p, hipStream_t s);
 int launch_wgrad_simt(int dtype, const GG& g, const WgradArgs& a, hipStream_t s);
 int launch_wgrad_rowdot(int dtype, const GG& g, const WgradArgs& a, hipStream_t s);
-int launch_wgrad_mfma(const GG& g, const WgradArgs& a, hipStream_t s);
+int launch_wgrad_mfma(const GG& g, const WgradArgs& a, const MfmaPlan& p, hipStream_t s);
 bool wgrad_mfma_ok(int dtype, const GG& g);
 bool thin_wgrad_conv_ok(int dtype, const GG& g);
 bool thin_wgrad_convt_ok(int dtype, const GG& g);

@@ -1,5 +1,6 @@
 // bf16 MFMA gather-GEMM kernels for gfx950 (v_mfma_f32_16x16x32_bf16, fp32 accumulate).  State at the end of round 4;
-// which kernel a call takes is decided in launch_fwd_mfma / launch_wgrad_mfma below and reported by pai_conv_kernel_name.
+// which kernel a call takes is decided ONCE, in fwd_mfma_plan / wgrad_mfma_plan below: the launchers switch on the plan's
+// variant, pai_conv_kernel_name and the row / byte queries read its fields.
 //
 // Forward / input-gradient:  out[m][co] = sum_{t,ci} A(m,t,ci) * Wp[co][wt][ci]
 //   gg_fwd_patch_k<256|128, 128|64> (+ gg_fwd_patch1_k<256, 64>) -- the kernels of the
@@ -62,7 +63,7 @@ static FwdCfg fwd_cfg(const GG& g) {
     c.ksplit = 1;
     const int ntiles = g.Cout / c.bn;
     const int niter = g.ntaps * g.Cin / MBK;
-    static const int mode = getenv("PAI_FWD_MODE") ? atoi(getenv("PAI_FWD_MODE")) : 0;
+    const int mode = env_int("PAI_FWD_MODE", 0);
     if (mode == 1 && c.bn == 128 && (int64_t)cdiv(g.M, 256) * ntiles * g.nphase >= 256 && niter >= 4) {
         c.bm = 256;
         return c;
@@ -73,8 +74,7 @@ static FwdCfg fwd_cfg(const GG& g) {
     }
     const int tiles = cdiv(g.M, 128) * ntiles * g.nphase;
     if (tiles >= 768 || niter < 8) return c;
-    static const int fixed_env = getenv("PAI_FWD_KSPLIT") ? atoi(getenv("PAI_FWD_KSPLIT")) : 0;
-    const int fixed = pai_tunable("fwd_ksplit", fixed_env);
+    const int fixed = pai_tunable("fwd_ksplit", env_int("PAI_FWD_KSPLIT", 0));
     if (fixed > 0) {
         int ks = fixed > niter / 2 ? niter / 2 : fixed;
         while (ks > 1 && (niter % ks)) --ks;
@@ -106,33 +106,6 @@ static FwdCfg fwd_cfg(const GG& g) {
 }
 
 constexpr int FIN_ROWS = 16;   // rows per split-K finish workgroup (= granularity of its BN partial statistics)
-
-int fwd_mfma_ksplit(const GG& g) { return fwd_cfg(g).ksplit; }
-
-int64_t fwd_mfma_workspace_bytes(const GG& g) {
-    const int ks = fwd_cfg(g).ksplit;
-    if (ks <= 1) return 0;
-    return (int64_t)ks * g.nphase * g.M * g.Cout * 4;   // one fp32 slab per K split
-}
-
-// the split actually used: only when the registered scratch is large enough
-static int fwd_effective_ksplit(const GG& g) {
-    const int ks = fwd_cfg(g).ksplit;
-    if (ks > 1 && (pai_ctx()->workspace == nullptr || pai_ctx()->workspace_bytes < fwd_mfma_workspace_bytes(g))) return 1;
-    return ks;
-}
-
-int fwd_mfma_ksplit_effective(const GG& g) { return fwd_effective_ksplit(g); }
-
-// number of BN partial-statistics rows per phase this launch configuration writes
-// rows per workgroup of the patch-resident kernel for this problem: 0 (not applicable), 128 or 256
-static int patch_rows(const GG& g, const FwdCfg& c);
-
-int fwd_mfma_mtiles(const GG& g) {
-    if (fwd_effective_ksplit(g) > 1) return cdiv(g.M, FIN_ROWS);
-    const FwdCfg c = fwd_cfg(g);
-    return patch_rows(g, c) == 256 ? g.M / 256 : cdiv(g.M, abs(c.bm));
-}
 
 
 // BM x BN x 64 tile, BM/64 x 2 waves of 64 x (BN/2).  DB = double-buffered LDS: the LDS-DMA of tile
@@ -569,28 +542,27 @@ __global__ __launch_bounds__(256) void splitk_finish_k(GG g, FwdArgs a, const fl
 // starting anywhere -- hit 16 different bank quads for every tap shift (the XOR only touches chunk
 // bits 1-2, the lane's own k-quarter keeps bit 0).
 
-static int patch_rows(const GG& g, const FwdCfg& c) {
-    static const bool no_patch = getenv("PAI_NO_PATCH") && atoi(getenv("PAI_NO_PATCH")) != 0;
-    static const bool no_256 = getenv("PAI_NO_PATCH256") && atoi(getenv("PAI_NO_PATCH256")) != 0;
-    if (no_patch || c.ksplit > 1 || c.bm != 128) return 0;
+// rows per workgroup of the patch-resident kernel for this problem: 0 (not applicable), 128 or 256 (then *pg is its geometry)
+static int patch_rows(const GG& g, const FwdCfg& c, PatchGeo* pg) {
+    const bool no_256 = env_int("PAI_NO_PATCH256", 0) != 0;
+    if (env_int("PAI_NO_PATCH", 0) || c.ksplit > 1 || c.bm != 128) return 0;
     // the kernel addresses its sources with 32-bit byte offsets into buffer descriptors
     if ((int64_t)g.N * g.H * g.W * (g.C1 > g.C2 ? g.C1 : g.C2) * 2 >= (1ll << 31) || (int64_t)g.Cout * g.wtaps * g.Cin * 2 >= (1ll << 31))
         return 0;
-    PatchGeo pg;
     // 16 x 16 tiles when the layer still fills the chip with them (two 8-wave workgroups per CU)
-    if (!no_256 && c.bn == 128 && (int64_t)(g.M / 256) * (g.Cout / 128) * g.nphase >= 512 && patch_geo(g, 16, &pg)) return 256;
+    if (!no_256 && c.bn == 128 && (int64_t)(g.M / 256) * (g.Cout / 128) * g.nphase >= 512 && patch_geo(g, 16, pg)) return 256;
     // 64-wide layers on 16 x 16 tiles with ONE wave column (gg_fwd_patch1_k, four waves of 64 x 64, three workgroups per
     // CU): pays where the reduction is long -- decoders[6] forward (two 128-channel sources, ReLU on load) 170 -> 158 us;
     // the input gradients of encoders[1] / D block 1 (128 channels deep) 91 -> 94 and 188 -> 189: left on the 8 x 16 tile.
     // With two weight-tile buffers (two workgroups per CU) every one of them is 5-25 % slower; two waves of 64 x 64 on the
     // 8 x 16 tile (128-thread workgroups) run those input gradients 13-22 % slower.  tunable fwd_w1 (default 1)
     if (!no_256 && c.bn == 64 && g.Cin >= 256 && pai_tunable("fwd_w1", 1) &&
-        (int64_t)(g.M / 256) * (g.Cout / 64) * g.nphase >= pai_tunable("fwd_w1_min", 768) && patch_geo(g, 16, &pg))
+        (int64_t)(g.M / 256) * (g.Cout / 64) * g.nphase >= pai_tunable("fwd_w1_min", 768) && patch_geo(g, 16, pg))
         return 256;
     // (measured and dropped: a 16 x 16 tile for the 64-wide layers -- decoders[6], input gradients of encoders[1] /
     // D block 1, whose LDS fill rather than the matrix pipe is the bound, scripts/abl.sh -- ran 10-25 % SLOWER than
     // the 8 x 16 tile at 4-5 workgroups per CU: 185 vs 166 us on decoders[6] forward)
-    return patch_geo(g, 8, &pg) ? 128 : 0;
+    return patch_geo(g, 8, pg) ? 128 : 0;
 }
 
 // Compile-time timing ablations of gg_fwd_patch_k (results are WRONG; scripts/abl.sh builds the variants):
@@ -1115,122 +1087,123 @@ template <int BM, int BN, bool DBB>
 __global__ __launch_bounds__(BM, 3) void gg_fwd_patch1_k(GG g, FwdArgs a, PatchGeo pg, int mtiles, int ntiles) {
     gg_fwd_patch_body<BM, BN, DBB, 1>(g, a, pg, mtiles, ntiles);
 }
-template <int BM, int BN, bool DB, int WR = 64>
-static size_t fwd_lds_bytes() {
-    const size_t main_loop = (size_t)(DB ? 2 : 1) * (BM * 128 + BN * 128);
-    const size_t epilogue = BM * (BN * 2 + 16) + (BM / WR * 2) * 2 * BN * sizeof(float);   // staged tile + [waves][2][BN]
+static size_t fwd_lds_bytes(int bm, int bn, bool db, int wr) {
+    const size_t main_loop = (size_t)(db ? 2 : 1) * (bm * 128 + bn * 128);
+    const size_t epilogue = bm * (bn * 2 + 16) + (bm / wr * 2) * 2 * bn * sizeof(float);   // staged tile + [waves][2][BN]
     return main_loop > epilogue ? main_loop : epilogue;
 }
 
-int launch_fwd_mfma(const GG& g, const FwdArgs& a, hipStream_t s) {
+// The variants of the family: X(id, argument form, kernel, template arguments).  The reported name IS the rocprofv3 symbol,
+// spelled from the same line the launch is instantiated from.
+#define FWD_MFMA_VARIANTS(X)                                         \
+    X(FWD_TILE256_DB, TILE, gg_fwd_mfma_k, 256, 128, false, true, 64)    \
+    X(FWD_TILE128_DB, TILE, gg_fwd_mfma_k, 128, 128, false, true, 64)    \
+    X(FWD_TILE128_W32, TILE, gg_fwd_mfma_k, 128, 128, false, false, 32)  \
+    X(FWD_SPLITK128_DB, TILE, gg_fwd_mfma_k, 128, 128, true, true, 64)   \
+    X(FWD_SPLITK128, TILE, gg_fwd_mfma_k, 128, 128, true, false, 64)     \
+    X(FWD_SPLITK64, TILE, gg_fwd_mfma_k, 128, 64, true, false, 64)       \
+    X(FWD_PATCH1_256_DBB, PATCH, gg_fwd_patch1_k, 256, 64, true)         \
+    X(FWD_PATCH1_256, PATCH, gg_fwd_patch1_k, 256, 64, false)            \
+    X(FWD_PATCH256_DBB, PATCH, gg_fwd_patch_k, 256, 128, true)           \
+    X(FWD_PATCH256, PATCH, gg_fwd_patch_k, 256, 128, false)              \
+    X(FWD_PATCH128_DBB, PATCH, gg_fwd_patch_k, 128, 128, true)           \
+    X(FWD_PATCH128, PATCH, gg_fwd_patch_k, 128, 128, false)              \
+    X(FWD_PATCH128N_DBB, PATCH, gg_fwd_patch_k, 128, 64, true)           \
+    X(FWD_PATCH128N, PATCH, gg_fwd_patch_k, 128, 64, false)              \
+    X(FWD_TILE128, TILE, gg_fwd_mfma_k, 128, 128, false, false, 64)      \
+    X(FWD_TILE64, TILE, gg_fwd_mfma_k, 128, 64, false, false, 64)
+#define X(id, form, k, ...) id,
+enum FwdMfmaVariant { FWD_MFMA_VARIANTS(X) };
+#undef X
+#define X(id, form, k, ...) #k "<" #__VA_ARGS__ ">",
+static const char* const fwd_mfma_names[] = {FWD_MFMA_VARIANTS(X)};
+#undef X
+
+MfmaPlan fwd_mfma_plan(const GG& g) {
+    MfmaPlan p = {};
     FwdCfg c = fwd_cfg(g);
-    c.ksplit = fwd_effective_ksplit(g);
-    const int mtiles = cdiv(g.M, abs(c.bm));
-    const int ntiles = g.Cout / c.bn;
-    const dim3 grid(mtiles * ntiles * g.nphase * c.ksplit);
-#define FWD_LAUNCH(BM, BN, SK, DB)                                                                  \
-    PAI_LAUNCH((gg_fwd_mfma_k<BM, BN, SK, DB>), grid, dim3(BM * 2), (fwd_lds_bytes<BM, BN, DB>()), s, g, \
-                       a, mtiles, ntiles, c.ksplit, pai_ctx()->workspace)
-    if (c.bm == 256) {
-        static PerDeviceOnce attr_set;   // > 64 KB of dynamic LDS needs an explicit opt-in
-        if (attr_set.first()) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gg_fwd_mfma_k<256, 128, false, true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)fwd_lds_bytes<256, 128, true>());
-            PAI_CHECK(e == hipSuccess, "hipFuncSetAttribute(max dynamic LDS): %s", hipGetErrorString(e));
-        }
-        FWD_LAUNCH(256, 128, false, true);
-    } else if (c.bm == -128) {
-        FWD_LAUNCH(128, 128, false, true);
-    } else if (c.bm == 128 && c.bn == 128 && c.ksplit == 1 && getenv("PAI_FWD_MODE") && atoi(getenv("PAI_FWD_MODE")) == 3) {
-        PAI_LAUNCH((gg_fwd_mfma_k<128, 128, false, false, 32>), grid, dim3(512),
-                           (fwd_lds_bytes<128, 128, false, 32>()), s, g, a, mtiles, ntiles, c.ksplit, pai_ctx()->workspace);
-    } else if (c.ksplit > 1) {
-        if (c.bn == 128) {
-            // two LDS stages (counted vmcnt + raw barrier): these launches have few workgroups and a long K loop per
-            // workgroup, i.e. nobody else hides their L2 -> LDS latency (encoders[4] forward 50 -> 45 us, decoders[3]
-            // input gradient 83 -> 76 us, scripts/micro/convbench)
-            if (pai_tunable("fwd_splitk_db", 1)) FWD_LAUNCH(128, 128, true, true); else FWD_LAUNCH(128, 128, true, false);
-        } else FWD_LAUNCH(128, 64, true, false);
-        PAI_LAUNCH_CHECK();
-        const int ftiles = cdiv(g.M, FIN_ROWS);
-        PAI_LAUNCH(splitk_finish_k, dim3(ftiles, g.nphase, cdiv(g.Cout, FIN_COLS)), dim3(256), 0, s, g, a,
-                           pai_ctx()->workspace, ftiles, c.ksplit);
+    p.workspace_bytes = c.ksplit > 1 ? (int64_t)c.ksplit * g.nphase * g.M * g.Cout * 4 : 0;   // one fp32 slab per K split
+    // the split actually used: only when the registered workspace holds the slabs
+    if (c.ksplit > 1 && (pai_ctx()->workspace == nullptr || pai_ctx()->workspace_bytes < p.workspace_bytes)) c.ksplit = 1;
+    p.ksplit = c.ksplit;
+    p.bm = abs(c.bm);
+    p.bn = c.bn;
+    p.mtiles = cdiv(g.M, p.bm);
+    p.ntiles = g.Cout / c.bn;
+    const int prow = patch_rows(g, c, &p.pg);
+    // statistics rows per phase: one per row tile, the split-K finish one per FIN_ROWS rows.  (PAI_FWD_MODE=3, a timing
+    // experiment, keeps reporting the rows of the patch kernel it displaces -- as before this function existed.)
+    p.rows = c.ksplit > 1 ? cdiv(g.M, FIN_ROWS) : (prow == 256 ? g.M / 256 : p.mtiles);
+    int wr = 64, waves = 0;         // waves > 0: a patch kernel
+    bool db = false;
+    // second weight-tile buffer: pays on the 128-wide tiles (bit 0: 256-row, bit 1: 128-row), not on the
+    // 64-wide ones (bit 2), whose 8 KB weight tile is cheap to wait for and which lose a workgroup per CU to it
+    const int dbb = env_int("PAI_PATCH_DBB", 3);
+    size_t patch_bytes = 0;
+    if (c.bm == 256) { p.variant = FWD_TILE256_DB; db = true; }
+    else if (c.bm == -128) { p.variant = FWD_TILE128_DB; db = true; }
+    else if (c.bn == 128 && c.ksplit == 1 && env_int("PAI_FWD_MODE", 0) == 3) { p.variant = FWD_TILE128_W32; wr = 32; }
+    else if (c.ksplit > 1) {
+        // two LDS stages (counted vmcnt + raw barrier): these launches have few workgroups and a long K loop per
+        // workgroup, i.e. nobody else hides their L2 -> LDS latency (encoders[4] forward 50 -> 45 us, decoders[3]
+        // input gradient 83 -> 76 us, scripts/micro/convbench)
+        db = c.bn == 128 && pai_tunable("fwd_splitk_db", 1);
+        p.variant = c.bn == 64 ? FWD_SPLITK64 : (db ? FWD_SPLITK128_DB : FWD_SPLITK128);
+    } else if (prow == 256 && c.bn == 64) {
+        db = (dbb & 4) != 0; waves = 4; patch_bytes = PatchDims<256, 1>::BYTES;
+        p.variant = db ? FWD_PATCH1_256_DBB : FWD_PATCH1_256;
+    } else if (prow == 256) {
+        db = (dbb & 1) != 0; waves = 8; patch_bytes = PatchDims<256>::BYTES;
+        p.variant = db ? FWD_PATCH256_DBB : FWD_PATCH256;
+    } else if (prow == 128) {
+        db = (dbb & (c.bn == 128 ? 2 : 4)) != 0; waves = 4; patch_bytes = PatchDims<128>::BYTES;
+        p.variant = c.bn == 128 ? (db ? FWD_PATCH128_DBB : FWD_PATCH128) : (db ? FWD_PATCH128N_DBB : FWD_PATCH128N);
+    } else p.variant = c.bn == 128 ? FWD_TILE128 : FWD_TILE64;
+    p.db = db;
+    p.name = fwd_mfma_names[p.variant];
+    if (waves) {
+        p.bm = prow;
+        p.mtiles = g.M / prow;      // (the geometry divides the image into whole tiles)
+        p.block = waves * 64;
+        const size_t lds = patch_bytes + (size_t)c.bn * 128 * (db ? 2 : 1);
+        const size_t epi = prow * ((size_t)c.bn * 2 + 16) + waves * 2 * c.bn * sizeof(float);
+        p.lds = lds > epi ? lds : epi;
     } else {
-        PatchGeo pg;
-        const int prow = patch_rows(g, c);
-        // second weight-tile buffer: pays on the 128-wide tiles (bit 0: 256-row, bit 1: 128-row), not on the
-        // 64-wide ones (bit 2), whose 8 KB weight tile is cheap to wait for and which lose a workgroup per CU to it
-        static const int dbb = getenv("PAI_PATCH_DBB") ? atoi(getenv("PAI_PATCH_DBB")) : 3;
-        if (prow == 256 && c.bn == 64 && patch_geo(g, 16, &pg)) {
-            typedef PatchDims<256, 1> PD;
-            const bool db = (dbb & 4) != 0;
-            const size_t lds = PD::BYTES + (size_t)64 * 128 * (db ? 2 : 1);
-            const size_t epi = 256 * ((size_t)64 * 2 + 16) + 4 * 2 * 64 * sizeof(float);
-            const size_t need = lds > epi ? lds : epi;
-            const int mt256 = g.M / 256;
-            const dim3 grid256(mt256 * ntiles * g.nphase);
-            if (db) PAI_LAUNCH((gg_fwd_patch1_k<256, 64, true>), grid256, dim3(256), need, s, g, a, pg, mt256, ntiles);
-            else PAI_LAUNCH((gg_fwd_patch1_k<256, 64, false>), grid256, dim3(256), need, s, g, a, pg, mt256, ntiles);
-        } else if (prow == 256 && patch_geo(g, 16, &pg)) {
-            typedef PatchDims<256> PD;
-            const bool db = (dbb & 1) != 0;
-            const size_t lds = PD::BYTES + (size_t)128 * 128 * (db ? 2 : 1);
-            const size_t epi = 256 * ((size_t)128 * 2 + 16) + 8 * 2 * 128 * sizeof(float);
-            const size_t need = lds > epi ? lds : epi;
-            static PerDeviceOnce attr;
-            if (attr.first()) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gg_fwd_patch_k<256, 128, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gg_fwd_patch_k<256, 128, false>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-                PAI_CHECK(e == hipSuccess, "hipFuncSetAttribute(max dynamic LDS): %s", hipGetErrorString(e));
-            }
-            const int mt256 = g.M / 256;
-            const dim3 grid256(mt256 * ntiles * g.nphase);
-            if (db) PAI_LAUNCH((gg_fwd_patch_k<256, 128, true>), grid256, dim3(512), need, s, g, a, pg, mt256, ntiles);
-            else PAI_LAUNCH((gg_fwd_patch_k<256, 128, false>), grid256, dim3(512), need, s, g, a, pg, mt256, ntiles);
-        } else if (prow == 128 && patch_geo(g, 8, &pg)) {
-            typedef PatchDims<128> PD;
-            const bool db = (dbb & (c.bn == 128 ? 2 : 4)) != 0;
-            const size_t lds = PD::BYTES + (size_t)c.bn * 128 * (db ? 2 : 1);
-            const size_t epi = 128 * ((size_t)c.bn * 2 + 16) + 4 * 2 * c.bn * sizeof(float);
-            const size_t need = lds > epi ? lds : epi;
-            if (c.bn == 128) {
-                if (db) PAI_LAUNCH((gg_fwd_patch_k<128, 128, true>), grid, dim3(256), need, s, g, a, pg, mtiles, ntiles);
-                else PAI_LAUNCH((gg_fwd_patch_k<128, 128, false>), grid, dim3(256), need, s, g, a, pg, mtiles, ntiles);
-            } else {
-                if (db) PAI_LAUNCH((gg_fwd_patch_k<128, 64, true>), grid, dim3(256), need, s, g, a, pg, mtiles, ntiles);
-                else PAI_LAUNCH((gg_fwd_patch_k<128, 64, false>), grid, dim3(256), need, s, g, a, pg, mtiles, ntiles);
-            }
-        } else if (c.bn == 128) FWD_LAUNCH(128, 128, false, false); else FWD_LAUNCH(128, 64, false, false);
+        p.block = p.bm / wr * 128;
+        p.lds = fwd_lds_bytes(p.bm, c.bn, db, wr);
     }
-#undef FWD_LAUNCH
+    p.grid = p.mtiles * p.ntiles * g.nphase * c.ksplit;
+    return p;
+}
+
+static int fwd_lds_opt_in();     // (defined below the switch, so that the kernels keep their order in the code object)
+int launch_fwd_mfma(const GG& g, const FwdArgs& a, const MfmaPlan& p, hipStream_t s) {
+    float* ws = pai_ctx()->workspace;
+    if (p.lds > 64 * 1024 && fwd_lds_opt_in()) return 1;
+#define FWD_LAUNCH_TILE(k, ...) PAI_LAUNCH((k<__VA_ARGS__>), p.grid, p.block, p.lds, s, g, a, p.mtiles, p.ntiles, p.ksplit, ws)
+#define FWD_LAUNCH_PATCH(k, ...) PAI_LAUNCH((k<__VA_ARGS__>), p.grid, p.block, p.lds, s, g, a, p.pg, p.mtiles, p.ntiles)
+#define X(id, form, k, ...) case id: FWD_LAUNCH_##form(k, __VA_ARGS__); break;
+    switch (p.variant) { FWD_MFMA_VARIANTS(X) }
+#undef X
+#undef FWD_LAUNCH_TILE
+#undef FWD_LAUNCH_PATCH
+    PAI_LAUNCH_CHECK();
+    if (p.ksplit > 1)
+        PAI_LAUNCH(splitk_finish_k, dim3(p.rows, g.nphase, cdiv(g.Cout, FIN_COLS)), dim3(256), 0, s, g, a, ws, p.rows, p.ksplit);
     PAI_LAUNCH_CHECK();
     return 0;
 }
-
-// rocprofv3-visible symbol of the main kernel launch_fwd_mfma picks for this problem (same decisions, no launch)
-const char* fwd_mfma_kernel_name(const GG& g) {
-    FwdCfg c = fwd_cfg(g);
-    c.ksplit = fwd_effective_ksplit(g);
-    const int mode = getenv("PAI_FWD_MODE") ? atoi(getenv("PAI_FWD_MODE")) : 0;
-    if (c.bm == 256) return "gg_fwd_mfma_k<256, 128, false, true, 64>";
-    if (c.bm == -128) return "gg_fwd_mfma_k<128, 128, false, true, 64>";
-    if (c.bm == 128 && c.bn == 128 && c.ksplit == 1 && mode == 3) return "gg_fwd_mfma_k<128, 128, false, false, 32>";
-    if (c.ksplit > 1)
-        return c.bn == 128 ? (pai_tunable("fwd_splitk_db", 1) ? "gg_fwd_mfma_k<128, 128, true, true, 64>" : "gg_fwd_mfma_k<128, 128, true, false, 64>")
-                           : "gg_fwd_mfma_k<128, 64, true, false, 64>";
-    const int dbb = getenv("PAI_PATCH_DBB") ? atoi(getenv("PAI_PATCH_DBB")) : 3;
-    const int prow = patch_rows(g, c);
-    if (prow == 256 && c.bn == 64) return (dbb & 4) ? "gg_fwd_patch1_k<256, 64, true>" : "gg_fwd_patch1_k<256, 64, false>";
-    if (prow == 256) return (dbb & 1) ? "gg_fwd_patch_k<256, 128, true>" : "gg_fwd_patch_k<256, 128, false>";
-    if (prow == 128) {
-        if (c.bn == 128) return (dbb & 2) ? "gg_fwd_patch_k<128, 128, true>" : "gg_fwd_patch_k<128, 128, false>";
-        return (dbb & 4) ? "gg_fwd_patch_k<128, 64, true>" : "gg_fwd_patch_k<128, 64, false>";
-    }
-    return c.bn == 128 ? "gg_fwd_mfma_k<128, 128, false, false, 64>" : "gg_fwd_mfma_k<128, 64, false, false, 64>";
+// > 64 KB of dynamic LDS needs an explicit opt-in, once per device: the kernels on 256-row tiles
+static int fwd_lds_opt_in() {
+    static PerDeviceOnce attr_set;
+    if (!attr_set.first()) return 0;
+    const void* fns[3] = {reinterpret_cast<const void*>(&gg_fwd_mfma_k<256, 128, false, true>),
+                          reinterpret_cast<const void*>(&gg_fwd_patch_k<256, 128, true>),
+                          reinterpret_cast<const void*>(&gg_fwd_patch_k<256, 128, false>)};
+    hipError_t e = hipFuncSetAttribute(fns[0], hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwd_lds_bytes(256, 128, true, 64));
+    for (int i = 1; i < 3 && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    PAI_CHECK(e == hipSuccess, "hipFuncSetAttribute(max dynamic LDS): %s", hipGetErrorString(e));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1944,43 +1917,29 @@ static bool wgrad_patch_shape_ok(const GG& g) {
     return g.lw >= 4 && g.lh >= 2 && (g.C1 % 32) == 0 && (g.C2 % 32) == 0 && (g.Cout % 64) == 0 && g.Cin >= 64;
 }
 
-static int wgrad_mfma_splits(const GG& g, int* rows_out);
-static bool wgrad_mfma_uses_patch(const GG& g) {
-    static const bool no_patch = getenv("PAI_NO_WPATCH") && atoi(getenv("PAI_NO_WPATCH")) != 0;
-    PatchGeo pg;
-    return !no_patch && wgrad_patch_shape_ok(g) && patch_geo(g, 4, &pg);
-}
-bool wgrad_mfma_can_overwrite(const GG& g) {
-    int rows;
-    if (wgrad3_ok(g)) return wgrad3_overwrites(g);
-    // un-split gg_wgrad_mfma_k: one writer per dW element (the taps of different phases are disjoint); the bias sums of
-    // several phases meet by atomics, launch_wgrad_mfma clears dbias for them
-    return !wgrad_mfma_uses_patch(g) && wgrad_mfma_splits(g, &rows) == 1;
+static bool wgrad_mfma_uses_patch(const GG& g, PatchGeo* pg) {
+    return !env_int("PAI_NO_WPATCH", 0) && wgrad_patch_shape_ok(g) && patch_geo(g, 4, pg);
 }
 
 // 128-channel tiles unless the layer would then run as at most one un-split workgroup per CU (the bottleneck layers:
 // <= 512 tiles, <= 2048 pixels): every K step of a lone workgroup is an exposed fill -> barrier -> multiply round trip, and
 // 64-channel tiles put two or more workgroups on a CU (tunable wgrad_narrow; convbench, us: encoders[5] 51.9 -> 37.5, [6] 24.7 ->
 // 18.4, [7] 19.2 -> 13.8, decoders[0] 19.5 -> 14.5, [1] 35.1 -> 31.3, [2] 63.5 -> 62.5; bit-identical on integer data)
-static bool wgrad_mfma_big(const GG& g) {
+static bool wgrad_mfma_big(const GG& g, bool patch) {
     if ((g.Cout % 128) != 0) return false;
     const int narrow = pai_tunable("wgrad_narrow", 512);      // 64-channel tiles up to this many 128-channel tiles (0: never)
-    if (narrow && !wgrad_mfma_uses_patch(g)) {
+    if (narrow && !patch) {
         const int tiles128 = (g.Cout / 128) * cdiv(g.ntaps * g.Cin, 128) * g.nphase;
         if (tiles128 <= narrow && g.M <= 2048) return false;
     }
     return true;
 }
 
-static int wgrad_mfma_splits(const GG& g, int* rows_out) {
-    const bool big = wgrad_mfma_big(g);
-    const int cotiles = big ? g.Cout / 128 : cdiv(g.Cout, 64);
-    const int jtiles = cdiv(g.ntaps * g.Cin, 128);
-    const int tiles = cotiles * jtiles * g.nphase;
+static int wgrad_mfma_splits(const GG& g, bool patch, int tiles, int* rows_out) {
     // Split of the pixel range: enough workgroups to fill the chip (3 per CU for the 128-wide tile, 4 for the
     // lighter 64-wide one), but every split adds one fp32 atomic pass over dW -- for the small-image layers
     // that pass, not the MFMA loop, is the cost, so a split never gets fewer than 512 pixels.
-    static const int target_env = getenv("PAI_WGRAD_TARGET") ? atoi(getenv("PAI_WGRAD_TARGET")) : 0;
+    const int target_env = env_int("PAI_WGRAD_TARGET", 0);
     const int target_tun = pai_tunable("wgrad_target", 0);
     // gg_wgrad_patch_k fits four workgroups per CU (128 VGPRs), gg_wgrad_mfma_k<128> three.  Measured per layer
     // (scripts/micro/convbench --set wgrad_target=...): the 137-GFLOP layers (decoders[4-6], D blocks 1-3 at 2N) want
@@ -1988,17 +1947,16 @@ static int wgrad_mfma_splits(const GG& g, int* rows_out) {
     // everything on gg_wgrad_mfma_k two (512: 86-88 us against 95-99 at 1024; encoders[4] 62 against 67 at 768) -- there
     // the extra atomic passes over dW cost more than the better balance buys.
     const double gflop = 2.0 * (double)g.M * g.nphase * g.Cout * g.ntaps * g.Cin * 1e-9;
-    const int target_def = (wgrad_mfma_uses_patch(g) && gflop >= 100.0) ? 1024 : 512;
+    const int target_def = (patch && gflop >= 100.0) ? 1024 : 512;
     const int target = target_tun ? target_tun : (target_env ? target_env : target_def);
     int splits = cdiv(target, tiles);
-    static const int min_rows = getenv("PAI_WGRAD_MINROWS") ? atoi(getenv("PAI_WGRAD_MINROWS")) : 512;
-    const int max_splits = cdiv(g.M, min_rows);
+    const int max_splits = cdiv(g.M, env_int("PAI_WGRAD_MINROWS", 512));
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     // An un-split launch owns every dW element in exactly one workgroup and updates it with a plain
     // read-modify-write; a split one adds splits x |dW| bytes of float atomics (~1.3 TB/s chip-wide).  For the
     // bottleneck layers (<= 2048 pixels, 4-8 M weights) those atomics were the whole cost.
-    static const int unsplit_rows = getenv("PAI_WGRAD_UNSPLIT_ROWS") ? atoi(getenv("PAI_WGRAD_UNSPLIT_ROWS")) : 2048;
+    const int unsplit_rows = env_int("PAI_WGRAD_UNSPLIT_ROWS", 2048);
     if ((tiles >= 256 && g.M <= unsplit_rows) || (tiles >= 512 && g.M <= 2 * unsplit_rows)) splits = 1;
     int rows = cdiv(cdiv(g.M, splits), 64) * 64;
     splits = cdiv(g.M, rows);
@@ -2011,56 +1969,49 @@ bool wgrad_pro_ok(int dtype, const GG& g) {
     return wgrad_mfma_ok(dtype, g) && g.ntaps == 1 && g.nphase == 1 && g.C2 == 0 && !g.gslice && !g.relu1 && !wgrad3_ok(g);
 }
 
-int launch_wgrad_mfma(const GG& g, const WgradArgs& a, hipStream_t s) {
-    if (a.pscale && !wgrad_pro_ok(PAI_BF16, g)) {
-        pai_set_error("launch_wgrad_mfma: this layer's weight gradient takes no prologue");
-        return 1;
+MfmaPlan wgrad_mfma_plan(const GG& g, bool has_dbias, bool has_prologue) {
+    MfmaPlan p = wgrad3_plan(g, has_dbias);      // gg_wgrad_patch3_k where it applies (gg_wg3.hip)
+    if (p.variant) return p;
+    const bool patch = wgrad_mfma_uses_patch(g, &p.pg), big = wgrad_mfma_big(g, patch);
+    p.bm = big ? 128 : 64;
+    p.mtiles = big ? g.Cout / 128 : cdiv(g.Cout, 64);     // output-channel tiles
+    p.ntiles = cdiv(g.ntaps * g.Cin, 128);                // (tap, input channel) tiles
+    const int tiles = p.mtiles * p.ntiles * g.nphase;
+    p.ksplit = wgrad_mfma_splits(g, patch, tiles, &p.rows);
+    // un-split gg_wgrad_mfma_k: one writer per dW element (the taps of different phases are disjoint); the bias sums of
+    // several phases meet by atomics, launch_wgrad_mfma clears dbias for them
+    p.overwrites = !patch && p.ksplit == 1;
+    p.block = 256;
+    if (patch && !has_prologue) {
+        p.variant = big ? WGRAD_PATCH128 : WGRAD_PATCH64;
+        p.name = big ? "gg_wgrad_patch_k<128>" : "gg_wgrad_patch_k<64>";
+        p.rows /= 64;                                     // here: 64-pixel K blocks per split
+        p.ksplit = cdiv(g.M / 64, p.rows);
+        p.lds = 64 * 256 + 128 * 64;
+    } else {
+        p.variant = big ? WGRAD_TILE128 : WGRAD_TILE64;
+        p.name = big ? "gg_wgrad_mfma_k<128>" : "gg_wgrad_mfma_k<64>";
+        // un-split pointwise layers store their tile as whole rows through LDS (see the kernel)
+        p.db = p.ksplit == 1 && g.ntaps == 1 && g.nphase == 1 && (g.Cin % 4) == 0 && !g.gslice && pai_tunable("wgrad_stage", 1) != 0;
+        p.lds = p.db ? 64 * 132 * 4 : 2 * 64 * 256;
     }
-    if (wgrad3_ok(g)) return launch_wgrad3(g, a, s);
-    const bool big = wgrad_mfma_big(g);
-    const int cotiles = big ? g.Cout / 128 : cdiv(g.Cout, 64);
-    const int jtiles = cdiv(g.ntaps * g.Cin, 128);
-    const int tiles = cotiles * jtiles * g.nphase;
-    int rows;
-    const int splits = wgrad_mfma_splits(g, &rows);
-    static const bool no_patch = getenv("PAI_NO_WPATCH") && atoi(getenv("PAI_NO_WPATCH")) != 0;
-    PatchGeo pg;
-    if (!a.pscale && !no_patch && wgrad_patch_shape_ok(g) && patch_geo(g, 4, &pg)) {
-        const int kblocks = g.M / 64;
-        const int per = rows / 64;
-        const int psplits = cdiv(kblocks, per);
-        const size_t plds = 64 * 256 + 128 * 64;
-        dim3 pgrid(tiles * psplits);
-        if (big)
-            PAI_LAUNCH(gg_wgrad_patch_k<128>, pgrid, dim3(256), plds, s, g, a, pg, cotiles, jtiles, psplits, per);
-        else
-            PAI_LAUNCH(gg_wgrad_patch_k<64>, pgrid, dim3(256), plds, s, g, a, pg, cotiles, jtiles, psplits, per);
-        PAI_LAUNCH_CHECK();
-        return 0;
-    }
-    // un-split pointwise layers store their tile as whole rows through LDS (see the kernel)
-    const int stage = splits == 1 && g.ntaps == 1 && g.nphase == 1 && (g.Cin % 4) == 0 && !g.gslice &&
-                      pai_tunable("wgrad_stage", 1) != 0;
-    const size_t lds = stage ? 64 * 132 * 4 : 2 * 64 * 256;
-    dim3 grid(tiles * splits);
-    if (a.overwrite_bias && a.dbias && g.nphase > 1) {
+    p.grid = tiles * p.ksplit;
+    return p;
+}
+
+int launch_wgrad_mfma(const GG& g, const WgradArgs& a, const MfmaPlan& p, hipStream_t s) {
+    if (p.variant < WGRAD_PATCH128) return launch_wgrad3(g, a, p, s);
+    const bool tile = p.variant == WGRAD_TILE128 || p.variant == WGRAD_TILE64;
+    if (tile && a.overwrite_bias && a.dbias && g.nphase > 1) {
         hipError_t e = pai::memset_async(a.dbias, 0, (size_t)g.Cout * sizeof(float), s);
         PAI_CHECK(e == hipSuccess, "launch_wgrad_mfma: hipMemsetAsync: %s", hipGetErrorString(e));
     }
-    if (big)
-        PAI_LAUNCH(gg_wgrad_mfma_k<128>, grid, dim3(256), lds, s, g, a, cotiles, jtiles, splits, rows, stage);
-    else
-        PAI_LAUNCH(gg_wgrad_mfma_k<64>, grid, dim3(256), lds, s, g, a, cotiles, jtiles, splits, rows, stage);
+    switch (p.variant) {
+        case WGRAD_PATCH128: PAI_LAUNCH(gg_wgrad_patch_k<128>, p.grid, p.block, p.lds, s, g, a, p.pg, p.mtiles, p.ntiles, p.ksplit, p.rows); break;
+        case WGRAD_PATCH64: PAI_LAUNCH(gg_wgrad_patch_k<64>, p.grid, p.block, p.lds, s, g, a, p.pg, p.mtiles, p.ntiles, p.ksplit, p.rows); break;
+        case WGRAD_TILE128: PAI_LAUNCH(gg_wgrad_mfma_k<128>, p.grid, p.block, p.lds, s, g, a, p.mtiles, p.ntiles, p.ksplit, p.rows, p.db); break;
+        default: PAI_LAUNCH(gg_wgrad_mfma_k<64>, p.grid, p.block, p.lds, s, g, a, p.mtiles, p.ntiles, p.ksplit, p.rows, p.db); break;
+    }
     PAI_LAUNCH_CHECK();
     return 0;
-}
-
-const char* wgrad_mfma_kernel_name(const GG& g) {
-    if (wgrad3_ok(g)) return wgrad3_kernel_name(g);
-    const bool big = wgrad_mfma_big(g);
-    const bool no_patch = getenv("PAI_NO_WPATCH") && atoi(getenv("PAI_NO_WPATCH")) != 0;
-    PatchGeo pg;
-    if (!no_patch && wgrad_patch_shape_ok(g) && patch_geo(g, 4, &pg))
-        return big ? "gg_wgrad_patch_k<128>" : "gg_wgrad_patch_k<64>";
-    return big ? "gg_wgrad_mfma_k<128>" : "gg_wgrad_mfma_k<64>";
 }

@@ -257,48 +257,55 @@ static void pwx_launch(const GG& g, const FwdArgs& a, int blocks, int gpw, hipSt
         else PAI_LAUNCH((pwx_k<CIN, COUT, T, 0, false, NSPLIT>), dim3(blocks), dim3(256), 0, s, g, a, gpw);
     }
 }
+// The one decision of the family: the instantiation pwx_k<cin, cout, t, MODE, PRE, nsplit> (MODE and PRE follow the arguments,
+// pwx_launch), its grid, and the reported name: the symbol with the LAYER's two channel counts and nothing after them.
+struct PwxPlan { int cin, cout, t, nsplit, blocks, gpw; char name[32]; };
+static PwxPlan pwx_plan(const GG& g, const FwdArgs& a) {
+    PwxPlan p;
+    p.nsplit = g.Cin * g.Cout > 128 * 128 ? 2 : 1;          // pixel streams per workgroup: 4 / nsplit
+    p.cin = g.Cin;
+    p.cout = g.Cout / p.nsplit;
+    p.t = p.nsplit == 2 ? 2 : pai_tunable("pwx_t", g.Cin * g.Cout > 64 * 128 ? 2 : 4);
+    if (g.Cout == 256 && p.nsplit == 1 && (a.stats || a.bz)) p.t = 1;   // (the 64-register statistics on top of a 128-register filter)
+    p.t = p.t >= 4 ? 4 : (p.t >= 2 ? 2 : 1);
+    p.blocks = pwx_rows(g);
+    const int64_t ngroups = ((int64_t)g.M + 15) / 16, streams = (int64_t)p.blocks * (4 / p.nsplit);
+    p.gpw = (int)((ngroups + streams - 1) / streams);
+    snprintf(p.name, sizeof(p.name), "pwx_k<%d, %d>", g.Cin, g.Cout);
+    return p;
+}
+
+constexpr int pwx_key(int nsplit, int cin, int cout) { return (nsplit * 1024 + cin) * 1024 + cout; }
 template <int CIN, int COUT>
-static void pwx_launch_t(const GG& g, const FwdArgs& a, int blocks, int gpw, int t, hipStream_t s) {
-    if (t >= 4) pwx_launch<CIN, COUT, 4>(g, a, blocks, gpw, s);
-    else if (t >= 2) pwx_launch<CIN, COUT, 2>(g, a, blocks, gpw, s);
-    else pwx_launch<CIN, COUT, 1>(g, a, blocks, gpw, s);
+static void pwx_launch_t(const GG& g, const FwdArgs& a, const PwxPlan& p, hipStream_t s) {
+    if (p.t == 4) pwx_launch<CIN, COUT, 4>(g, a, p.blocks, p.gpw, s);
+    else if (p.t == 2) pwx_launch<CIN, COUT, 2>(g, a, p.blocks, p.gpw, s);
+    else pwx_launch<CIN, COUT, 1>(g, a, p.blocks, p.gpw, s);
 }
 
 int launch_pwx(const GG& g, const FwdArgs& a, hipStream_t s) {
-    const int blocks = pwx_rows(g);
-    const int64_t ngroups = ((int64_t)g.M + 15) / 16;
-    const int ci = g.Cin, co = g.Cout;
-    const int nsplit = ci * co > 128 * 128 ? 2 : 1;          // pixel streams per workgroup: 4 / nsplit
-    const int gpw = (int)((ngroups + (int64_t)blocks * (4 / nsplit) - 1) / ((int64_t)blocks * (4 / nsplit)));
-    if (nsplit == 2) {
-        if (ci == 128 && co == 256) pwx_launch<128, 128, 2, 2>(g, a, blocks, gpw, s);
-        else if (ci == 256 && co == 128) pwx_launch<256, 64, 2, 2>(g, a, blocks, gpw, s);
-        else {
-            pai_set_error("launch_pwx: no instantiation for %d -> %d channels", ci, co);
+    const PwxPlan p = pwx_plan(g, a);
+    switch (pwx_key(p.nsplit, p.cin, p.cout)) {
+        case pwx_key(2, 128, 128): pwx_launch<128, 128, 2, 2>(g, a, p.blocks, p.gpw, s); break;
+        case pwx_key(2, 256, 64): pwx_launch<256, 64, 2, 2>(g, a, p.blocks, p.gpw, s); break;
+        case pwx_key(1, 64, 64): pwx_launch_t<64, 64>(g, a, p, s); break;
+        case pwx_key(1, 64, 128): pwx_launch_t<64, 128>(g, a, p, s); break;
+        case pwx_key(1, 128, 64): pwx_launch_t<128, 64>(g, a, p, s); break;
+        case pwx_key(1, 128, 128): pwx_launch_t<128, 128>(g, a, p, s); break;
+        case pwx_key(1, 256, 64): pwx_launch_t<256, 64>(g, a, p, s); break;
+        case pwx_key(1, 64, 256): pwx_launch_t<64, 256>(g, a, p, s); break;
+        default:
+            pai_set_error("launch_pwx: no instantiation for %d -> %d channels", g.Cin, g.Cout);
             return 1;
-        }
-        PAI_LAUNCH_CHECK();
-        return 0;
-    }
-    const int big = ci * co > 64 * 128;
-    int t = pai_tunable("pwx_t", big ? 2 : 4);
-    if (co == 256 && (a.stats || a.bz)) t = 1;                     // (the 64-register statistics on top of a 128-register filter)
-    if (ci == 64 && co == 64) pwx_launch_t<64, 64>(g, a, blocks, gpw, t, s);
-    else if (ci == 64 && co == 128) pwx_launch_t<64, 128>(g, a, blocks, gpw, t, s);
-    else if (ci == 128 && co == 64) pwx_launch_t<128, 64>(g, a, blocks, gpw, t, s);
-    else if (ci == 128 && co == 128) pwx_launch_t<128, 128>(g, a, blocks, gpw, t, s);
-    else if (ci == 256 && co == 64) pwx_launch_t<256, 64>(g, a, blocks, gpw, t, s);
-    else if (ci == 64 && co == 256) pwx_launch_t<64, 256>(g, a, blocks, gpw, t, s);
-    else {
-        pai_set_error("launch_pwx: no instantiation for %d -> %d channels", ci, co);
-        return 1;
     }
     PAI_LAUNCH_CHECK();
     return 0;
 }
 
 const char* pwx_kernel_name(const GG& g) {
-    static thread_local char buf[48];
-    snprintf(buf, sizeof(buf), "pwx_k<%d, %d>", g.Cin, g.Cout);
-    return buf;
+    static thread_local PwxPlan p;
+    FwdArgs a;
+    memset(&a, 0, sizeof(a));
+    p = pwx_plan(g, a);
+    return p.name;
 }

@@ -142,16 +142,6 @@ __device__ __forceinline__ void bwd_write_partials(float* sred, const float* s1,
     }
 }
 
-struct PatchGeo {
-    int groups;                    // windows per phase: 1 or 4
-    int TY, TX;                    // 8 x 16 tiles per image
-    signed char by[4][4], bx[4][4];  // [phase][window] source offset of patch pixel (0,0) from (gy0*S, gx0*S)
-    unsigned toff4[4][4];          // 4 x 8 bit: patch offset ty*17+tx of the window's taps
-    unsigned wt4[4][4];            // 4 x 8 bit: weight tap slot of the window's taps
-    // the same per phase, packed for the forward kernel's scalar registers (patch_geo_pack): weight tap slots 4 bits per
-    // (window, tap) -- windows 0-1 in wt_lo, 2-3 in wt_hi -- and patch offsets (ty, tx) 2 bits per (window, tap)
-    unsigned wt_lo[4], wt_hi[4], toff2[4];
-};
 constexpr int PATCH_W = 17;
 // BM = 128: 8 x 16 output pixels, 4 waves;  BM = 256: 16 x 16 output pixels, 8 waves (4 x 2) -- the weight
 // tile fill is then shared by twice the rows: 25 KB of fill and 128 KB of fragment reads per 2 x 512

@@ -869,84 +869,78 @@ int launch_wgrad_slab_sum(float* dw, const float* slab, int nsplits, int64_t n, 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------
-static int wg3_variant(const GG& g) {   // 0: not eligible, 1: <128, 64>, 2: <64, 128>, 3: <128, 64> on 8 x 8-pixel K steps
+// 0: not eligible, else the WG3_* variant (<128, 64>, <64, 128>, <128, 64> on 8 x 8-pixel K steps) and its patch geometry
+static int wg3_variant(const GG& g, PatchGeo* pg) {
     const int mode = pai_tunable("wgrad3", 7);   // bit 0: the 128 x 64 wave tile, bit 1: the 64 x 128 one, bit 2: 8 x 8-pixel K steps; 0: round-2 kernels
     if (!mode) return 0;
-    PatchGeo pg;
     // 32-bit byte offsets into buffer descriptors: every tensor below 2 GB
     if ((int64_t)g.N * g.H * g.W * (g.C1 > g.C2 ? g.C1 : g.C2) * 2 >= (1ll << 31) || (int64_t)g.N * g.OH * g.OW * g.Cout * 2 >= (1ll << 31))
         return 0;
-    if (g.lsw >= 0 && g.lw == 3 && g.lh >= 3 && patch_geo(g, 8, &pg, 8))    // 8-wide images (encoders[4], decoders[3])
-        return ((mode & 4) && (g.Cout % 128) == 0 && (g.C1 % 64) == 0 && (g.C2 % 64) == 0 && g.Cin >= 64) ? 3 : 0;
-    if (!(g.lsw >= 0 && g.lw >= 4 && g.lh >= 2 && patch_geo(g, 4, &pg))) return 0;
-    if ((g.Cout % 128) == 0 && (g.C1 % 64) == 0 && (g.C2 % 64) == 0 && g.Cin >= 64) return (mode & 1) ? 1 : 0;
-    if ((g.Cout % 64) == 0 && (g.C1 % 128) == 0 && (g.C2 % 128) == 0 && g.Cin >= 128) return (mode & 2) ? 2 : 0;
+    if (g.lsw >= 0 && g.lw == 3 && g.lh >= 3 && patch_geo(g, 8, pg, 8))    // 8-wide images (encoders[4], decoders[3])
+        return ((mode & 4) && (g.Cout % 128) == 0 && (g.C1 % 64) == 0 && (g.C2 % 64) == 0 && g.Cin >= 64) ? WG3_128x64_8 : 0;
+    if (!(g.lsw >= 0 && g.lw >= 4 && g.lh >= 2 && patch_geo(g, 4, pg))) return 0;
+    if ((g.Cout % 128) == 0 && (g.C1 % 64) == 0 && (g.C2 % 64) == 0 && g.Cin >= 64) return (mode & 1) ? WG3_128x64 : 0;
+    if ((g.Cout % 64) == 0 && (g.C1 % 128) == 0 && (g.C2 % 128) == 0 && g.Cin >= 128) return (mode & 2) ? WG3_64x128 : 0;
     return 0;
 }
 
-bool wgrad3_ok(const GG& g) { return wg3_variant(g) != 0; }
-
-struct Wg3Cfg { int bmc, ci, cotiles, jtiles, tiles, psplits, per; };
-
-static Wg3Cfg wg3_cfg(const GG& g, int solo = -1) {      // solo: -1 = as the problem says, 0 / 1 = forced (workspace sizing)
+bool wgrad3_ok(const GG& g) {
     PatchGeo pg;
-    const int v = wg3_variant(g);
-    if (v == 3) patch_geo(g, 8, &pg, 8); else patch_geo(g, 4, &pg);
-    Wg3Cfg c;
-    c.bmc = v == 2 ? 64 : 128;
-    c.ci = v == 2 ? 128 : 64;
-    c.cotiles = g.Cout / c.bmc;
-    c.jtiles = (g.Cin / c.ci) * pg.groups;
-    c.tiles = c.cotiles * c.jtiles * g.nphase;
+    return wg3_variant(g, &pg) != 0;
+}
+
+// pixel splits: ONE workgroup per CU (256).  Alone on the chip two per CU (512) are faster (scripts/micro/convbench), but
+// in the training step the weight gradients run beside the input-gradient chain of the main stream: with 256
+// workgroups they flush half the slab bytes (32 instead of 64 MB per layer, and wgrad_slab_sum_k reads half) and leave
+// the other half of every CU to the main stream -- same-box step, two interleaved runs each: 6.36 ms at 256, 6.42-6.44
+// at 192, 6.49 at 384, 6.55 at 512, 6.67 at 768, 7.05 at 128.  A split never gets fewer than 512 pixels.
+// PAI_HINT_SOLO (the last weight gradients of a backward pass: the input-gradient chain has ended, the main stream only
+// waits for them): two workgroups per CU, the grid that is fastest alone (D block 1: 292 -> ~180 us in the step's tail).
+static int wg3_psplits(const GG& g, int tiles, int solo, int* per) {
     const int kblocks = g.M / 64;
-    // pixel splits: ONE workgroup per CU (256).  Alone on the chip two per CU (512) are faster (scripts/micro/convbench), but
-    // in the training step the weight gradients run beside the input-gradient chain of the main stream: with 256
-    // workgroups they flush half the slab bytes (32 instead of 64 MB per layer, and wgrad_slab_sum_k reads half) and leave
-    // the other half of every CU to the main stream -- same-box step, two interleaved runs each: 6.36 ms at 256, 6.42-6.44
-    // at 192, 6.49 at 384, 6.55 at 512, 6.67 at 768, 7.05 at 128.  A split never gets fewer than 512 pixels.
-    // PAI_HINT_SOLO (the last weight gradients of a backward pass: the input-gradient chain has ended, the main stream only
-    // waits for them): two workgroups per CU, the grid that is fastest alone (D block 1: 292 -> ~180 us in the step's tail).
-    if (solo < 0) solo = g.solo;
-    int splits = cdiv(solo ? pai_tunable("wgrad3_target_solo", 512) : pai_tunable("wgrad3_target", 256), c.tiles);
+    int splits = cdiv(solo ? pai_tunable("wgrad3_target_solo", 512) : pai_tunable("wgrad3_target", 256), tiles);
     const int max_splits = cdiv(g.M, pai_tunable("wgrad3_minrows", 512));
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
-    c.per = cdiv(kblocks, splits);
-    c.psplits = cdiv(kblocks, c.per);
-    return c;
+    *per = cdiv(kblocks, splits);
+    return cdiv(kblocks, *per);
 }
 
-int64_t wgrad3_slab_bytes(const GG& g) {
-    if (!wgrad3_ok(g)) return 0;
-    const Wg3Cfg c0 = wg3_cfg(g, 0), c1 = wg3_cfg(g, 1);     // the workspace serves the layer with and without PAI_HINT_SOLO
-    const int ps = c0.psplits > c1.psplits ? c0.psplits : c1.psplits;
-    return ps > 1 ? (int64_t)ps * g.Cout * g.wtaps * g.Cin * 4 : 0;
+// variant 0: not this family.  rows = 64-pixel K blocks per split, db = the pipelined K loop.  The name omits the trailing
+// ", 0" of the non-pipelined form (include/pai_hip.h, pai_conv_kernel_name).
+MfmaPlan wgrad3_plan(const GG& g, bool has_dbias) {
+    static const char* const names[3] = {"gg_wgrad_patch3_k<128, 64, 16>", "gg_wgrad_patch3_k<64, 128, 16>", "gg_wgrad_patch3_k<128, 64, 8>"};
+    MfmaPlan p = {};
+    const int v = wg3_variant(g, &p.pg);
+    if (!v) return p;
+    p.variant = v;
+    p.name = names[v - WG3_128x64];
+    p.bm = v == WG3_64x128 ? 64 : 128;
+    p.bn = v == WG3_64x128 ? 128 : 64;
+    p.mtiles = g.Cout / p.bm;
+    p.ntiles = (g.Cin / p.bn) * p.pg.groups;
+    const int tiles = p.mtiles * p.ntiles * g.nphase;
+    p.ksplit = wg3_psplits(g, tiles, g.solo, &p.rows);
+    int per;      // the workspace serves the layer with and without PAI_HINT_SOLO
+    const int ps0 = wg3_psplits(g, tiles, 0, &per), ps1 = wg3_psplits(g, tiles, 1, &per), ps = ps0 > ps1 ? ps0 : ps1;
+    const int64_t dw_bytes = (int64_t)g.Cout * g.wtaps * g.Cin * 4;
+    p.workspace_bytes = ps > 1 ? ps * dw_bytes : 0;
+    // pai_conv_wgrad_overwrite needs no zero fill: every dW element has one writer (un-split: the taps of different phases
+    // are disjoint) or the slab sum writes it
+    p.overwrites = p.ksplit == 1 || (pai_tunable("wgrad_slab", 1) && wgrad_slab_acquire(p.ksplit * dw_bytes) != nullptr);
+    // the pipelined K loop (see the kernel): not with a bias gradient (the bias sums live in the round-3 loop only)
+    p.db = pai_tunable("wgrad3_pipe", 1) && !has_dbias;
+    p.lds = (size_t)2 * (v == WG3_128x64 ? 64 * 256 + 96 * 128 : (v == WG3_64x128 ? 64 * 128 + 96 * 256 : 64 * 256 + 128 * 128));
+    p.grid = tiles * p.ksplit;
+    p.block = 256;
+    return p;
 }
 
-// pai_conv_wgrad_overwrite needs no zero fill: every dW element has one writer (un-split: the taps of different phases
-// are disjoint) or the slab sum writes it
-bool wgrad3_overwrites(const GG& g) {
-    if (!wgrad3_ok(g)) return false;
-    const Wg3Cfg c = wg3_cfg(g);
-    if (c.psplits == 1) return true;
-    return pai_tunable("wgrad_slab", 1) && wgrad_slab_acquire((int64_t)c.psplits * g.Cout * g.wtaps * g.Cin * 4) != nullptr;
-}
-
-const char* wgrad3_kernel_name(const GG& g) {
-    const int v = wg3_variant(g);
-    return v == 1 ? "gg_wgrad_patch3_k<128, 64, 16>" : (v == 2 ? "gg_wgrad_patch3_k<64, 128, 16>" : "gg_wgrad_patch3_k<128, 64, 8>");
-}
-
-int launch_wgrad3(const GG& g, const WgradArgs& a0, hipStream_t s) {
-    PatchGeo pg;
-    const int variant = wg3_variant(g);
-    PAI_CHECK(variant != 0 && (variant == 3 ? patch_geo(g, 8, &pg, 8) : patch_geo(g, 4, &pg)), "launch_wgrad3: problem not eligible");
-    const Wg3Cfg c = wg3_cfg(g);
+int launch_wgrad3(const GG& g, const WgradArgs& a0, const MfmaPlan& p, hipStream_t s) {
     WgradArgs a = a0;
     const int64_t dwn = (int64_t)g.Cout * g.wtaps * g.Cin;
-    const int64_t need = (int64_t)c.psplits * dwn * 4;
     float* slab = nullptr;
-    if (c.psplits > 1 && pai_tunable("wgrad_slab", 1)) slab = wgrad_slab_acquire(need);
+    if (p.ksplit > 1 && pai_tunable("wgrad_slab", 1)) slab = wgrad_slab_acquire((int64_t)p.ksplit * dwn * 4);
     a.slab = slab;
     if (a.overwrite_bias && a.dbias) {   // the bias sums of the workgroups meet by atomics
         hipError_t e = pai::memset_async(a.dbias, 0, (size_t)g.Cout * sizeof(float), s);
@@ -961,24 +955,17 @@ int launch_wgrad3(const GG& g, const WgradArgs& a0, hipStream_t s) {
         for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
         PAI_CHECK(e == hipSuccess, "hipFuncSetAttribute(max dynamic LDS): %s", hipGetErrorString(e));
     }
-    const dim3 grid(c.tiles * c.psplits);
     const int ph_inner = g.nphase > 1 && pai_tunable("wgrad3_ph_inner", 1);
-    // the pipelined K loop (see the kernel): not with a bias gradient (the bias sums live in the round-3 loop only)
-    const int pipe = pai_tunable("wgrad3_pipe", 1) && !a.dbias;
-    if (variant == 1) {
-        const size_t lds = (size_t)2 * (64 * 256 + 96 * 128);
-        if (pipe) PAI_LAUNCH((gg_wgrad_patch3_k<128, 64, 16>), grid, dim3(256), lds, s, g, a, pg, c.cotiles, c.jtiles, c.psplits, c.per, ph_inner);
-        else PAI_LAUNCH((gg_wgrad_patch3_k<128, 64, 16, 0>), grid, dim3(256), lds, s, g, a, pg, c.cotiles, c.jtiles, c.psplits, c.per, ph_inner);
-    } else if (variant == 2) {
-        const size_t lds = (size_t)2 * (64 * 128 + 96 * 256);
-        if (pipe) PAI_LAUNCH((gg_wgrad_patch3_k<64, 128, 16>), grid, dim3(256), lds, s, g, a, pg, c.cotiles, c.jtiles, c.psplits, c.per, ph_inner);
-        else PAI_LAUNCH((gg_wgrad_patch3_k<64, 128, 16, 0>), grid, dim3(256), lds, s, g, a, pg, c.cotiles, c.jtiles, c.psplits, c.per, ph_inner);
-    } else {
-        const size_t lds = (size_t)2 * (64 * 256 + 128 * 128);
-        if (pipe) PAI_LAUNCH((gg_wgrad_patch3_k<128, 64, 8>), grid, dim3(256), lds, s, g, a, pg, c.cotiles, c.jtiles, c.psplits, c.per, ph_inner);
-        else PAI_LAUNCH((gg_wgrad_patch3_k<128, 64, 8, 0>), grid, dim3(256), lds, s, g, a, pg, c.cotiles, c.jtiles, c.psplits, c.per, ph_inner);
+#define WG3_LAUNCH(...)                                                                                                          \
+    if (p.db) PAI_LAUNCH((gg_wgrad_patch3_k<__VA_ARGS__>), p.grid, p.block, p.lds, s, g, a, p.pg, p.mtiles, p.ntiles, p.ksplit, p.rows, ph_inner); \
+    else PAI_LAUNCH((gg_wgrad_patch3_k<__VA_ARGS__, 0>), p.grid, p.block, p.lds, s, g, a, p.pg, p.mtiles, p.ntiles, p.ksplit, p.rows, ph_inner)
+    switch (p.variant) {
+        case WG3_128x64: WG3_LAUNCH(128, 64, 16); break;
+        case WG3_64x128: WG3_LAUNCH(64, 128, 16); break;
+        default: WG3_LAUNCH(128, 64, 8); break;
     }
+#undef WG3_LAUNCH
     PAI_LAUNCH_CHECK();
-    if (slab) return launch_wgrad_slab_sum(a.dw, slab, c.psplits, dwn, a.overwrite, s);
+    if (slab) return launch_wgrad_slab_sum(a.dw, slab, p.ksplit, dwn, a.overwrite, s);
     return 0;
 }
