@@ -43,6 +43,7 @@ extern "C" {
 #define PAI_ACT_LRELU 1   /* LeakyReLU(0.2)  models/pix2pix.py:62, models/wrapper.py:205 */
 #define PAI_ACT_RELU 2    /* ReLU            models/pix2pix.py:98 */
 #define PAI_ACT_TANH 3    /* Tanh            models/pix2pix.py:196 */
+#define PAI_ACT_SILU 4    /* v * sigmoid(v)  models/guided_diffusion/unet.py:18-20; pai_affine_act only */
 
 const char* pai_last_error(void);
 /* 100: round 1.  110: per-device handles, pai_set_tunable, pai_adam_dev, pai_scalar_take / pai_metrics_take,
@@ -58,7 +59,8 @@ const char* pai_last_error(void);
  * 132: input prologue (pai_conv_prologue_ok, pai_conv_fwd_pro, pai_conv_wgrad_pro); pai_instnorm_fwd / _bwd; pai_bn2_bwd_reduce / _apply; pai_bn_stats_buffer_rows grows for
  * layers with more than 2048 partial rows (callers that size the buffer through it need no change).
  * 133: device-resident data set (pai_resize_aa_u8, pai_batch_gather, pai_data_kernel_name), PAI_U8.
- * 134: report evaluation (pai_eval_planes, pai_eval_kernel_name). */
+ * 134: report evaluation (pai_eval_planes, pai_eval_kernel_name).
+ * 135: Palette sampling (pai_sattn_fwd, pai_affine_act, pai_film_coeffs, pai_avgpool2, pai_gamma_embedding, pai_palette_step), PAI_ACT_SILU. */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -719,6 +721,42 @@ int pai_resize_aa_u8(const void* src, int n, int H, int W, int S, const int* wbo
 int pai_batch_gather(int src_dtype, const void* cache_a, const void* cache_b, int64_t M, int64_t per_image,
                      const int64_t* indices, int count, const float* table, float* out_a, float* out_b, void* stream);
 int pai_data_kernel_name(int op, int src_dtype, char* name, int name_len);
+
+/* ---------------------------------------------------------------------------
+ * Palette sampling: the eval-mode guided-diffusion U-Net and the reverse diffusion step (reference models/palette.py:79-100,
+ * 233-306, models/guided_diffusion/unet.py, nn.py).  Forward only.  Tensors are 16-byte aligned.
+ *
+ * pai_sattn_fwd: QKVAttentionLegacy (unet.py:265-297) over the T tokens of a level.  qkv [N][T][heads * 3 * ch] is the NHWC
+ * output of the 1 x 1 qkv convolution in the reference's channel order [head][q | k | v][ch]; out [N][T][heads * ch], head h
+ * in columns h * ch ...  out = softmax((q s)(k s)^T) v per (n, head) with s = ch ** -0.25; s * s multiplies the fp32 scores.
+ * The T x T scores are never stored: online softmax with fp32 running maximum and sum and an fp32 output accumulator,
+ * rescaled at every key tile.  ch in {32, 64, 128, 256}, any other value is refused; T >= 1, a key tail that is not a whole
+ * tile is masked, not read.  PAI_BF16: both products on the matrix cores, the probabilities and the output each rounded
+ * once to bf16.  PAI_F32: exact fp32 FMA chains (the parity mode).
+ * pai_affine_act: out = act(x * A + B) on [N][rows_per_sample][C], C a multiple of 8 and at most 2048; A, B fp32 [C]
+ * (per_sample = 0) or [N][C] (per_sample = 1); act PAI_ACT_NONE | PAI_ACT_SILU.  Every BatchNorm (eval) + SiLU site of the
+ * U-Net, with FiLM folded into per-sample coefficients, and the bare SiLU (A = 1, B = 0).  out may alias x.
+ * pai_film_coeffs: A[n][c] = a[c] (1 + scale[n][c]), B[n][c] = b[c] (1 + scale[n][c]) + shift[n][c] from the BatchNorm eval
+ * coefficients a, b (pai_bn_eval_coeffs) and emb_out (dtype) [N] rows of ld elements: scale = the first C columns of a row,
+ * shift = the next C ("use_scale_shift_norm", unet.py:206-210).
+ * pai_avgpool2: out [N][H/2][W/2][C] = the 2 x 2 mean of x [N][H][W][C] (AvgPool2d(2), unet.py:98); H, W even, C % 8 == 0.
+ * pai_gamma_embedding: out (dtype) [N][dim] = [cos(g f_i) | sin(g f_i) | 0 if dim is odd], f_i = exp(-ln(10000) i / (dim / 2))
+ * (nn.py:140-157).
+ * pai_palette_step: one reverse step on `pixels` pixels of C channels, [pixel][channel].  model_out (dtype) has C columns
+ * (eps) or, learn_var, 2 C (eps | variance interpolation); y_t, noise, y_next fp32.  y0 = clamp((y_t - s1 eps) rs, -1, 1),
+ * mean = c0 y0 + c1 y_t, log variance = v log_hi + (1 - v) log_lo with v = (var + 1) / 2 (learn_var) or log_lo,
+ * y_next = mean + exp(log variance / 2) noise when add_noise, else mean.  xy_next (dtype, optional) [pixel][2 C]: the columns
+ * C .. 2 C - 1 get y_next -- the y half of the [x | y_t] tensor the next U-Net call reads.  y_next may alias y_t. */
+int pai_sattn_fwd(int dtype, const void* qkv, int N, int T, int heads, int ch, void* out, void* stream);
+int pai_affine_act(int dtype, const void* x, int64_t rows_per_sample, int N, int C, const float* A, const float* B,
+                   int per_sample, int act, void* out, void* stream);
+int pai_film_coeffs(int dtype, int C, int N, const float* a, const float* b, const void* emb_out, int64_t ld, float* A,
+                    float* B, void* stream);
+int pai_avgpool2(int dtype, const void* x, int N, int H, int W, int C, void* out, void* stream);
+int pai_gamma_embedding(int dtype, const float* gammas, int N, int dim, void* out, void* stream);
+int pai_palette_step(int dtype, const void* model_out, const float* y_t, const float* noise, int64_t pixels, int C,
+                     int learn_var, int add_noise, float s1, float rs, float c0, float c1, float log_lo, float log_hi,
+                     float* y_next, void* xy_next, void* stream);
 
 #ifdef __cplusplus
 }

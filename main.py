@@ -42,8 +42,8 @@ def main(hparams):
                                  dropout=hparams.dropout, loss_type=hparams.loss_type)
     elif hparams.model == "palette":
         raise NotImplementedError(
-            "model 'palette' (the diffusion model) is outside the U-Net / Pix2Pix hot path this build covers "
-            "(SURVEY.md section 8)")
+            "model 'palette': training (training_step, the VLB term, the LinearLR schedule, the backward passes) is not "
+            "built; sampling is -- pai.Palette loads a checkpoint and report.py -m palette evaluates it (DESIGN.md 7c)")
     else:
         raise ValueError(f"Incorrect model name ({hparams.model})")
 

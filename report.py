@@ -102,6 +102,8 @@ def output_hot_image(img: torch.Tensor, filename: str, clock=None):
 
 def count_macs(model) -> int:
     unet = getattr(model, "unet", None)
+    if isinstance(model, pai.Palette):       # one sampling call: inference_steps U-Net passes (conv + linear + attention)
+        return model.diffusion_inf.timesteps * unet.macs(256, 256)
     if unet is not None and hasattr(unet, "vit_bottleneck"):      # TransUNet: convs at their output resolution + ViT
         def conv_macs(c, sp_out):
             return sp_out * sp_out * c.weight.shape[0] * c.weight.shape[1] * c.weight.shape[2] * c.weight.shape[3]
@@ -163,6 +165,9 @@ def main(hparams):
         model.freeze()
     elif hparams.model == "trans_unet":
         model = pai.TransUnetGAN.load_from_checkpoint(hparams.checkpoint, map_location=dev)
+        model.freeze()
+    elif hparams.model == "palette":
+        model = pai.Palette.load_from_checkpoint(hparams.checkpoint, map_location=dev)
         model.freeze()
     elif hparams.model == "identity":
         def model(x):

@@ -1,0 +1,513 @@
+// Palette sampling (reference models/palette.py:79-100,233-306 and models/guided_diffusion/unet.py, nn.py): the kernels the
+// eval-mode guided-diffusion U-Net and the reverse step need beside the convolution family.
+//
+//   pai_sattn_fwd        QKVAttentionLegacy (unet.py:265-297) over the T = H * W tokens of a level, flash style: the T x T
+//                        scores are never stored.  bf16: one workgroup of four waves per 128 queries of one (image, head),
+//                        each wave 32 queries, the K / V tiles shared through LDS.  Both products run on
+//                        v_mfma_f32_32x32x16_bf16 in the orientation that keeps every per-query quantity on the query's own
+//                        lane: S^T = K Q^T has the query on the lane and the keys in the 16 registers, and O^T = V^T P^T
+//                        takes that accumulator, rounded to bf16, directly as its B operand and again has the query on
+//                        the lane -- running max, running sum and the rescale factor never cross lanes except for the one
+//                        exchange between the two lane halves that split a query's keys.  V^T fragments come from a
+//                        row-major LDS image through ds_read_b64_tr_b16 in the k order the accumulator imposes.  The
+//                        rescale happens at every tile (no deferred maximum).  fp32 (parity mode): a vector-ALU kernel with
+//                        the same online softmax, sequential FMA chains.
+//   pai_affine_act       out = act(x * A + B), A / B per channel or per (sample, channel): every BatchNorm (eval) + SiLU
+//                        site of the network, FiLM included.
+//   pai_film_coeffs      A = a (1 + scale), B = b (1 + scale) + shift from the BatchNorm eval coefficients and emb_out.
+//   pai_avgpool2         2 x 2 mean (Downsample(use_conv=False)).
+//   pai_gamma_embedding  [cos(g f_i) | sin(g f_i)] (nn.py:140-157).
+//   pai_palette_step     one reverse diffusion step, elementwise (palette.py:233-306).
+#include "common.h"
+
+#include <math.h>
+
+typedef __attribute__((ext_vector_type(8))) __bf16 pbf8_t;
+typedef __attribute__((ext_vector_type(4))) __bf16 pbf4_t;
+typedef __attribute__((ext_vector_type(16))) float pf16_t;
+
+// ---- spatial self-attention, bf16 -------------------------------------------------------------------------------------------
+// LDS images of a K / V tile: rows of CH bf16, the 16-byte chunks of a row permuted by an XOR that depends on the row.
+//   K is read row-wise (ds_read_b128: lane = key row, one chunk per k-step): the XOR spreads the 16 rows of a lane group
+//   over the 16 chunk slots of a 256-byte bank line.
+//   V is read through the transposed 4-row x 16-column blocks: the XOR moves the four rows of a block to different 64-byte
+//   quarters of the bank line.
+template <int CH> __device__ __forceinline__ int sattn_kswz(int row) {
+    constexpr int CPR = CH / 8;
+    if (CPR >= 16) return row & 15;
+    constexpr int SH = CPR == 8 ? 1 : 2;          // rows per 256 bytes: 2 (CH 64), 4 (CH 32)
+    return (row >> SH) & (CPR - 1);
+}
+template <int CH> __device__ __forceinline__ int sattn_vswz(int row) {
+    constexpr int CPR = CH / 8;
+    if (CPR >= 16) return (row & 3) << 2;
+    if (CPR == 8) return ((row >> 1) & 1) << 2;
+    return 0;
+}
+
+// A-operand fragment of O^T = V^T P^T for the 16 keys R0 .. R0 + 15 of the tile and the 32 channels d0 .. d0 + 31: element j
+// of lane (r = lane & 31, hh = lane >> 5) is V[R0 + 8 (j >> 2) + 4 hh + (j & 3)][d0 + r] -- the key order of registers
+// 8s .. 8s + 7 of the S^T accumulator.  Two transposed reads of 4 rows x 16 columns per 16-lane group.
+template <int CH>
+__device__ __forceinline__ pbf8_t sattn_vt_frag(const bf16_t* Vs, int R0, int d0, int lane) {
+    const int q = (lane & 15) >> 2, p = lane & 3, hh = lane >> 5;
+    const int col = d0 + 16 * ((lane >> 4) & 1) + 4 * p;
+    const int rlo = R0 + 4 * hh + q, rhi = rlo + 8;
+    const bf16_t* alo = Vs + rlo * CH + 8 * ((col >> 3) ^ sattn_vswz<CH>(rlo)) + (col & 7);
+    const bf16_t* ahi = Vs + rhi * CH + 8 * ((col >> 3) ^ sattn_vswz<CH>(rhi)) + (col & 7);
+    typedef pbf4_t __attribute__((address_space(3))) * lds4_t;
+    const pbf4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4_t)(const void*)alo);
+    const pbf4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4_t)(const void*)ahi);
+    return (pbf8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
+template <int CH>
+__global__ __launch_bounds__(256) void sattn_bf16_k(const bf16_t* qkv, int T, int heads, float scale2, bf16_t* out) {
+    constexpr int KVB = CH > 128 ? 32 : 64;       // keys per tile
+    constexpr int NS = KVB / 32;                  // 32-key sub-tiles
+    constexpr int CPR = CH / 8;                   // 16-byte chunks per row
+    constexpr int KS = CH / 16;                   // k-steps of S^T
+    constexpr int DB = CH / 32;                   // 32-channel blocks of O^T
+    constexpr bool QREG = CH <= 128;              // Q fragments stay in registers (CH 256: read again per tile, L1 hits)
+    __shared__ __attribute__((aligned(16))) bf16_t Ks[KVB * CH];
+    __shared__ __attribute__((aligned(16))) bf16_t Vs[KVB * CH];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r = lane & 31, hh = lane >> 5;
+    const int n = blockIdx.y / heads, h = blockIdx.y - n * heads;
+    const int64_t RS = (int64_t)heads * 3 * CH;
+    const bf16_t* base = qkv + (int64_t)n * T * RS + (int64_t)h * 3 * CH;
+    const int q0 = blockIdx.x * 128 + w * 32;
+    const bool active = q0 < T;                   // wave-uniform
+    const int qi = q0 + r;
+    const bf16_t* qrow = base + (int64_t)min(qi, T - 1) * RS;
+    pbf8_t qf[QREG ? KS : 1];
+    if (QREG) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = *(const pbf8_t*)(qrow + 16 * ks + 8 * hh);
+    }
+    pf16_t o[DB];
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) o[d][t] = 0.f;
+    float m = -INFINITY, l = 0.f;                 // running maximum (shared by the two lane halves) and this lane's part of the sum
+
+    for (int k0 = 0; k0 < T; k0 += KVB) {
+        __syncthreads();                          // the previous tile has been read
+        for (int c = tid; c < KVB * CPR; c += 256) {
+            const int row = c / CPR, ch = c - row * CPR;
+            uint4 kv = make_uint4(0, 0, 0, 0), vv = make_uint4(0, 0, 0, 0);
+            if (k0 + row < T) {                   // the key tail is zero-filled, never read
+                const bf16_t* src = base + (int64_t)(k0 + row) * RS + CH + 8 * ch;
+                kv = *(const uint4*)src;
+                vv = *(const uint4*)(src + CH);
+            }
+            *(uint4*)(Ks + row * CH + 8 * (ch ^ sattn_kswz<CH>(row))) = kv;
+            *(uint4*)(Vs + row * CH + 8 * (ch ^ sattn_vswz<CH>(row))) = vv;
+        }
+        __syncthreads();
+        if (!active) continue;
+        // S^T = K Q^T: D[row key][col query]; register t of lane (r, hh) is key 8 (t >> 2) + 4 hh + (t & 3) of the sub-tile
+        pf16_t s[NS];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int sb = 0; sb < NS; ++sb) {
+#pragma unroll
+            for (int t = 0; t < 16; ++t) s[sb][t] = 0.f;
+            const int krow = 32 * sb + r;
+            const bf16_t* kr = Ks + krow * CH;
+            const int kx = sattn_kswz<CH>(krow);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const pbf8_t kf = *(const pbf8_t*)(kr + 8 * ((2 * ks + hh) ^ kx));
+                const pbf8_t qv = QREG ? qf[QREG ? ks : 0] : *(const pbf8_t*)(qrow + 16 * ks + 8 * hh);
+                s[sb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qv, s[sb], 0, 0, 0);
+            }
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const int key = k0 + 32 * sb + 8 * (t >> 2) + 4 * hh + (t & 3);
+                const float v = key < T ? s[sb][t] * scale2 : -INFINITY;     // s * s on the fp32 score
+                s[sb][t] = v;
+                mx = fmaxf(mx, v);
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));   // the other half of this query's keys
+        const float mn = fmaxf(m, mx);            // finite: key k0 of every tile exists
+        const float alpha = __expf(m - mn);       // 0 at the first tile (m = -inf)
+        m = mn;
+        float ls = 0.f;
+        pbf8_t pf[NS][2];
+#pragma unroll
+        for (int sb = 0; sb < NS; ++sb)
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const float p = __expf(s[sb][t] - mn);
+                ls += p;
+                pf[sb][t >> 3][t & 7] = (__bf16)p;
+            }
+        l = fmaf(l, alpha, ls);
+        // O^T = O^T alpha + V^T P^T: D[row channel][col query]
+#pragma unroll
+        for (int d = 0; d < DB; ++d) {
+#pragma unroll
+            for (int t = 0; t < 16; ++t) o[d][t] *= alpha;
+#pragma unroll
+            for (int sb = 0; sb < NS; ++sb)
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2)
+                    o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sattn_vt_frag<CH>(Vs, 32 * sb + 16 * s2, 32 * d, lane),
+                                                                   pf[sb][s2], o[d], 0, 0, 0);
+        }
+    }
+    if (!active) return;
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / l;
+    if (qi < T) {
+        bf16_t* orow = out + ((int64_t)n * T + qi) * heads * CH + (int64_t)h * CH;
+#pragma unroll
+        for (int d = 0; d < DB; ++d)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {         // registers 4g .. 4g + 3: channels 32 d + 8 g + 4 hh + (0 .. 3)
+                uint2 pk;
+                pk.x = pk2bf(o[d][4 * g] * inv, o[d][4 * g + 1] * inv);
+                pk.y = pk2bf(o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv);
+                *(uint2*)(orow + 32 * d + 8 * g + 4 * hh) = pk;
+            }
+    }
+}
+
+// ---- spatial self-attention, fp32 (parity mode) -------------------------------------------------------------------------
+// 32 queries per workgroup, eight threads per query: each takes every eighth key of the tile for the scores and a slice of
+// the channels for the output.  Sequential FMA chains over the channels (scores) and over the keys (output).
+template <int CH, int KVB>
+__global__ __launch_bounds__(256) void sattn_f32_k(const float* qkv, int T, int heads, float scale2, float* out) {
+    constexpr int NE = KVB / 8, ND = CH / 32;
+    __shared__ __attribute__((aligned(16))) float Ks[KVB * CH];
+    __shared__ __attribute__((aligned(16))) float Vs[KVB * CH];
+    __shared__ float Ps[32][KVB + 1];
+    const int tid = threadIdx.x, ql = tid >> 3, g = tid & 7;
+    const int n = blockIdx.y / heads, h = blockIdx.y - n * heads;
+    const int64_t RS = (int64_t)heads * 3 * CH;
+    const float* base = qkv + (int64_t)n * T * RS + (int64_t)h * 3 * CH;
+    const int qi = blockIdx.x * 32 + ql;
+    const float* qrow = base + (int64_t)min(qi, T - 1) * RS;
+    float4 o[ND];
+#pragma unroll
+    for (int e = 0; e < ND; ++e) o[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    float m = -INFINITY, l = 0.f;
+    for (int k0 = 0; k0 < T; k0 += KVB) {
+        __syncthreads();
+        for (int c = tid; c < KVB * (CH / 4); c += 256) {
+            const int row = c / (CH / 4), c4 = c - row * (CH / 4);
+            float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
+            if (k0 + row < T) {
+                const float* src = base + (int64_t)(k0 + row) * RS + CH + 4 * c4;
+                kv = *(const float4*)src;
+                vv = *(const float4*)(src + CH);
+            }
+            *(float4*)(Ks + row * CH + 4 * c4) = kv;
+            *(float4*)(Vs + row * CH + 4 * c4) = vv;
+        }
+        __syncthreads();
+        float s[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) s[e] = 0.f;
+        for (int c = 0; c < CH; c += 4) {
+            const float4 qv = *(const float4*)(qrow + c);
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const float4 kv = *(const float4*)(Ks + (g + 8 * e) * CH + c);
+                s[e] = fmaf(qv.x, kv.x, s[e]);
+                s[e] = fmaf(qv.y, kv.y, s[e]);
+                s[e] = fmaf(qv.z, kv.z, s[e]);
+                s[e] = fmaf(qv.w, kv.w, s[e]);
+            }
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            s[e] = (k0 + g + 8 * e) < T ? s[e] * scale2 : -INFINITY;
+            mx = fmaxf(mx, s[e]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 4, 64));
+        const float mn = fmaxf(m, mx);
+        const float alpha = expf(m - mn);
+        m = mn;
+        float ls = 0.f;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const float p = expf(s[e] - mn);
+            Ps[ql][g + 8 * e] = p;
+            ls += p;
+        }
+        ls += __shfl_xor(ls, 1, 64);
+        ls += __shfl_xor(ls, 2, 64);
+        ls += __shfl_xor(ls, 4, 64);
+        l = fmaf(l, alpha, ls);
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < ND; ++e) { o[e].x *= alpha; o[e].y *= alpha; o[e].z *= alpha; o[e].w *= alpha; }
+        for (int k = 0; k < KVB; ++k) {
+            const float p = Ps[ql][k];
+#pragma unroll
+            for (int e = 0; e < ND; ++e) {
+                const float4 v = *(const float4*)(Vs + k * CH + 4 * g + 32 * e);
+                o[e].x = fmaf(p, v.x, o[e].x);
+                o[e].y = fmaf(p, v.y, o[e].y);
+                o[e].z = fmaf(p, v.z, o[e].z);
+                o[e].w = fmaf(p, v.w, o[e].w);
+            }
+        }
+    }
+    if (qi < T) {
+        float* orow = out + ((int64_t)n * T + qi) * heads * CH + (int64_t)h * CH;
+        const float inv = 1.0f / l;
+#pragma unroll
+        for (int e = 0; e < ND; ++e)
+            *(float4*)(orow + 4 * g + 32 * e) = make_float4(o[e].x * inv, o[e].y * inv, o[e].z * inv, o[e].w * inv);
+    }
+}
+
+extern "C" int pai_sattn_fwd(int dtype, const void* qkv, int N, int T, int heads, int ch, void* out, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_sattn_fwd: dtype=%d", dtype);
+    PAI_CHECK(qkv && out, "pai_sattn_fwd: null tensor");
+    PAI_CHECK(N >= 1 && T >= 1 && heads >= 1, "pai_sattn_fwd: N=%d T=%d heads=%d", N, T, heads);
+    PAI_CHECK(ch == 32 || ch == 64 || ch == 128 || ch == 256, "pai_sattn_fwd: ch=%d (32, 64, 128 or 256 channels per head)", ch);
+    PAI_CHECK((int64_t)N * heads <= 65535, "pai_sattn_fwd: N * heads = %lld (at most 65535)", (long long)N * heads);
+    PAI_CHECK((((uintptr_t)qkv) | ((uintptr_t)out)) % 16 == 0, "pai_sattn_fwd: tensors must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const float scale2 = 1.0f / sqrtf((float)ch);           // (ch ** -0.25) ** 2
+    if (dtype == PAI_BF16) {
+        const dim3 grid(cdiv(T, 128), N * heads);
+#define PAI_SATTN_BF16(CH) \
+    hipLaunchKernelGGL((sattn_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, T, heads, scale2, (bf16_t*)out)
+        switch (ch) {
+            case 32: PAI_SATTN_BF16(32); break;
+            case 64: PAI_SATTN_BF16(64); break;
+            case 128: PAI_SATTN_BF16(128); break;
+            default: PAI_SATTN_BF16(256); break;
+        }
+#undef PAI_SATTN_BF16
+    } else {
+        const dim3 grid(cdiv(T, 32), N * heads);
+#define PAI_SATTN_F32(CH, KVB) \
+    hipLaunchKernelGGL((sattn_f32_k<CH, KVB>), grid, dim3(256), 0, s, (const float*)qkv, T, heads, scale2, (float*)out)
+        switch (ch) {
+            case 32: PAI_SATTN_F32(32, 32); break;
+            case 64: PAI_SATTN_F32(64, 32); break;
+            case 128: PAI_SATTN_F32(128, 32); break;
+            default: PAI_SATTN_F32(256, 16); break;
+        }
+#undef PAI_SATTN_F32
+    }
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- out = act(x * A + B) -----------------------------------------------------------------------------------------------------
+// [N][rows][C], C = 8 G.  A workgroup covers 256 / G rows at a time; a thread keeps its channel group, so the coefficients
+// (per channel or per sample and channel) are loaded once, and has SV vectors in flight.
+constexpr int AV = 4;
+
+template <bool EXACT> __device__ __forceinline__ float silu_f(float v) {
+    return EXACT ? v / (1.0f + expf(-v)) : v / (1.0f + __expf(-v));
+}
+
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void affine_act_k(const T* x, int64_t rows, int G, int R, const float* A, const float* B,
+                                                    int per_sample, T* out) {
+    const int cg = threadIdx.x % G, rr = threadIdx.x / G;
+    if (rr >= R) return;
+    const int C = G * 8, n = blockIdx.y;
+    const float* ap = A + (per_sample ? (int64_t)n * C : 0) + cg * 8;
+    const float* bp = B + (per_sample ? (int64_t)n * C : 0) + cg * 8;
+    float a[8], b[8];
+    V8<float>::ld(ap, a);
+    V8<float>::ld(bp, b);
+    const T* xs = x + (int64_t)n * rows * C + cg * 8;
+    T* os = out + (int64_t)n * rows * C + cg * 8;
+    const int64_t step = (int64_t)gridDim.x * R * AV;
+    for (int64_t r0 = (int64_t)blockIdx.x * R * AV + rr; r0 < rows; r0 += step) {
+        float v[AV][8];
+#pragma unroll
+        for (int k = 0; k < AV; ++k)
+            if (r0 + (int64_t)k * R < rows) V8<T>::ld(xs + (r0 + (int64_t)k * R) * C, v[k]);
+#pragma unroll
+        for (int k = 0; k < AV; ++k)
+            if (r0 + (int64_t)k * R < rows) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float t = fmaf(v[k][e], a[e], b[e]);
+                    v[k][e] = ACT == PAI_ACT_SILU ? silu_f<sizeof(T) == 4>(t) : t;
+                }
+                V8<T>::st(os + (r0 + (int64_t)k * R) * C, v[k]);
+            }
+    }
+}
+
+extern "C" int pai_affine_act(int dtype, const void* x, int64_t rows_per_sample, int N, int C, const float* A, const float* B,
+                              int per_sample, int act, void* out, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_affine_act: dtype=%d", dtype);
+    PAI_CHECK(x && out && A && B, "pai_affine_act: null tensor");
+    PAI_CHECK(act == PAI_ACT_NONE || act == PAI_ACT_SILU, "pai_affine_act: act=%d (none or SiLU)", act);
+    PAI_CHECK(N >= 1 && N <= 65535 && rows_per_sample >= 1, "pai_affine_act: N=%d rows=%lld", N, (long long)rows_per_sample);
+    PAI_CHECK(C >= 8 && C % 8 == 0 && C <= 2048, "pai_affine_act: C=%d (a multiple of 8, at most 2048)", C);
+    const int G = C / 8, R = 256 / G;
+    const dim3 grid((unsigned)min((int64_t)4096, (rows_per_sample + (int64_t)R * AV - 1) / ((int64_t)R * AV)), N);
+    hipStream_t s = (hipStream_t)stream;
+#define PAI_AFF(TT, ACT) \
+    hipLaunchKernelGGL((affine_act_k<TT, ACT>), grid, dim3(256), 0, s, (const TT*)x, rows_per_sample, G, R, A, B, per_sample, (TT*)out)
+    if (dtype == PAI_F32) {
+        if (act == PAI_ACT_SILU) PAI_AFF(float, PAI_ACT_SILU); else PAI_AFF(float, PAI_ACT_NONE);
+    } else {
+        if (act == PAI_ACT_SILU) PAI_AFF(bf16_t, PAI_ACT_SILU); else PAI_AFF(bf16_t, PAI_ACT_NONE);
+    }
+#undef PAI_AFF
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- FiLM coefficients ------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void film_coeffs_k(int C, int N, const float* a, const float* b, const T* emb, int64_t ld,
+                                                     float* A, float* B) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N * C) return;
+    const int n = i / C, c = i - n * C;
+    const float sc = 1.0f + Conv<T>::ld(emb + n * ld + c), sh = Conv<T>::ld(emb + n * ld + C + c);
+    A[i] = a[c] * sc;
+    B[i] = fmaf(b[c], sc, sh);
+}
+
+extern "C" int pai_film_coeffs(int dtype, int C, int N, const float* a, const float* b, const void* emb_out, int64_t ld,
+                               float* A, float* B, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_film_coeffs: dtype=%d", dtype);
+    PAI_CHECK(a && b && emb_out && A && B, "pai_film_coeffs: null tensor");
+    PAI_CHECK(C >= 1 && N >= 1 && ld >= 2 * (int64_t)C && (int64_t)N * C < (1ll << 31), "pai_film_coeffs: C=%d N=%d ld=%lld", C, N,
+              (long long)ld);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == PAI_F32)
+        hipLaunchKernelGGL(film_coeffs_k<float>, dim3(cdiv((int64_t)N * C, 256)), dim3(256), 0, s, C, N, a, b, (const float*)emb_out, ld, A, B);
+    else
+        hipLaunchKernelGGL(film_coeffs_k<bf16_t>, dim3(cdiv((int64_t)N * C, 256)), dim3(256), 0, s, C, N, a, b, (const bf16_t*)emb_out, ld, A, B);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- 2 x 2 mean ---------------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void avgpool2_k(const T* x, int64_t nvec, int OH, int OW, int G, T* out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvec) return;
+    const int cg = (int)(i % G);
+    int64_t p = i / G;
+    const int ox = (int)(p % OW);
+    p /= OW;
+    const int oy = (int)(p % OH);
+    const int64_t n = p / OH;
+    const int C = G * 8, W = 2 * OW;
+    const T* s = x + (((n * 2 * OH + 2 * oy) * W + 2 * ox) * (int64_t)C) + cg * 8;
+    float a[8], b[8], c[8], d[8];
+    V8<T>::ld(s, a);
+    V8<T>::ld(s + C, b);
+    V8<T>::ld(s + (int64_t)W * C, c);
+    V8<T>::ld(s + (int64_t)W * C + C, d);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = ((a[e] + b[e]) + (c[e] + d[e])) * 0.25f;
+    V8<T>::st(out + i * 8, a);
+}
+
+extern "C" int pai_avgpool2(int dtype, const void* x, int N, int H, int W, int C, void* out, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_avgpool2: dtype=%d", dtype);
+    PAI_CHECK(x && out, "pai_avgpool2: null tensor");
+    PAI_CHECK(N >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "pai_avgpool2: N=%d H=%d W=%d (even sizes)", N, H, W);
+    PAI_CHECK(C >= 8 && C % 8 == 0, "pai_avgpool2: C=%d (a multiple of 8)", C);
+    const int64_t nvec = (int64_t)N * (H / 2) * (W / 2) * (C / 8);
+    PAI_CHECK((nvec + 255) / 256 < (1ll << 31), "pai_avgpool2: tensor too large");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((nvec + 255) / 256));
+    if (dtype == PAI_F32)
+        hipLaunchKernelGGL(avgpool2_k<float>, grid, dim3(256), 0, s, (const float*)x, nvec, H / 2, W / 2, C / 8, (float*)out);
+    else
+        hipLaunchKernelGGL(avgpool2_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, nvec, H / 2, W / 2, C / 8, (bf16_t*)out);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- sinusoidal embedding of the noise level ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void gamma_embedding_k(const float* gammas, int N, int dim, T* out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N * dim) return;
+    const int n = i / dim, j = i - n * dim, half = dim / 2;
+    float v = 0.f;                                // the last column of an odd dim
+    if (j < 2 * half) {
+        const int k = j < half ? j : j - half;
+        const double arg = (double)gammas[n] * exp(-9.210340371976184 /* ln 10000 */ * (double)k / (double)half);
+        v = (float)(j < half ? cos(arg) : sin(arg));
+    }
+    Conv<T>::st(out + i, v);
+}
+
+extern "C" int pai_gamma_embedding(int dtype, const float* gammas, int N, int dim, void* out, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_gamma_embedding: dtype=%d", dtype);
+    PAI_CHECK(gammas && out, "pai_gamma_embedding: null tensor");
+    PAI_CHECK(N >= 1 && dim >= 2 && (int64_t)N * dim < (1ll << 31), "pai_gamma_embedding: N=%d dim=%d", N, dim);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == PAI_F32)
+        hipLaunchKernelGGL(gamma_embedding_k<float>, dim3(cdiv((int64_t)N * dim, 256)), dim3(256), 0, s, gammas, N, dim, (float*)out);
+    else
+        hipLaunchKernelGGL(gamma_embedding_k<bf16_t>, dim3(cdiv((int64_t)N * dim, 256)), dim3(256), 0, s, gammas, N, dim, (bf16_t*)out);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- one reverse step ------------------------------------------------------------------------------------------------------------------
+// y0 = clamp((y_t - s1 eps) rs, -1, 1); mean = c0 y0 + c1 y_t; log variance = v log_hi + (1 - v) log_lo with v = (var + 1) / 2
+// (learn_var) or log_lo; y_{t-1} = mean + exp(0.5 log variance) noise (add_noise) -- the expression order of
+// palette.py:233-306.  Pixels are [pixel][channel]; the model output has C (or, learn_var, 2 C: eps | var) columns.
+template <typename T>
+__global__ __launch_bounds__(256) void palette_step_k(const T* mo, const float* y_t, const float* noise, int64_t numel, int C,
+                                                      int learn_var, int add_noise, float s1, float rs, float c0, float c1,
+                                                      float log_lo, float log_hi, float* y_next, T* xy_next) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= numel) return;
+    const int64_t px = i / C;
+    const int c = (int)(i - px * C);
+    const int Cm = learn_var ? 2 * C : C;
+    const float eps = Conv<T>::ld(mo + px * Cm + c), y = y_t[i];
+    // one rounding for y_t - s1 eps: rs reaches 800 at the first step, and a rounded product would cost 1e-4 of y0 there
+    float y0 = rs * fmaf(-s1, eps, y);
+    y0 = fminf(fmaxf(y0, -1.f), 1.f);
+    const float mean = c0 * y0 + c1 * y;
+    float lv = log_lo;
+    if (learn_var) {
+        const float vi = (Conv<T>::ld(mo + px * Cm + C + c) + 1.f) * 0.5f;
+        lv = vi * log_hi + (1.f - vi) * log_lo;
+    }
+    const float out = add_noise ? mean + expf(0.5f * lv) * noise[i] : mean;
+    y_next[i] = out;
+    if (xy_next) Conv<T>::st(xy_next + px * 2 * C + C + c, out);
+}
+
+extern "C" int pai_palette_step(int dtype, const void* model_out, const float* y_t, const float* noise, int64_t pixels, int C,
+                                int learn_var, int add_noise, float s1, float rs, float c0, float c1, float log_lo, float log_hi,
+                                float* y_next, void* xy_next, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_palette_step: dtype=%d", dtype);
+    PAI_CHECK(model_out && y_t && y_next && (noise || !add_noise), "pai_palette_step: null tensor");
+    PAI_CHECK(pixels >= 1 && C >= 1, "pai_palette_step: pixels=%lld C=%d", (long long)pixels, C);
+    const int64_t numel = pixels * C;
+    PAI_CHECK((numel + 255) / 256 < (1ll << 31), "pai_palette_step: tensor too large");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((numel + 255) / 256));
+    if (dtype == PAI_F32)
+        hipLaunchKernelGGL(palette_step_k<float>, grid, dim3(256), 0, s, (const float*)model_out, y_t, noise, numel, C, learn_var,
+                           add_noise, s1, rs, c0, c1, log_lo, log_hi, y_next, (float*)xy_next);
+    else
+        hipLaunchKernelGGL(palette_step_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)model_out, y_t, noise, numel, C, learn_var,
+                           add_noise, s1, rs, c0, c1, log_lo, log_hi, y_next, (bf16_t*)xy_next);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("PAI_HIP_LIB") or os.path.join(HERE, "libpai_hip.so")
 F32, BF16 = 0, 1
 U8 = 2          # PAI_U8: image bytes of the device-resident data set
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
+ACT_SILU = 4       # PAI_ACT_SILU: pai_affine_act only
 HINT_SOLO = 1
 
 
@@ -182,6 +183,12 @@ SIGNATURES = {
     "pai_resize_aa_u8": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "pai_batch_gather": (_I, [_I, _P, _P, _L, _L, _P, _I, _P, _P, _P, _P]),
     "pai_data_kernel_name": (_I, [_I, _I, C.c_char_p, _I]),
+    "pai_sattn_fwd": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
+    "pai_affine_act": (_I, [_I, _P, _L, _I, _I, _P, _P, _I, _I, _P, _P]),
+    "pai_film_coeffs": (_I, [_I, _I, _I, _P, _P, _P, _L, _P, _P, _P]),
+    "pai_avgpool2": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
+    "pai_gamma_embedding": (_I, [_I, _P, _I, _I, _P, _P]),
+    "pai_palette_step": (_I, [_I, _P, _P, _P, _L, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
 }
 
 _lib = None

@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import lib as L
-from .lib import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, BF16, F32, U8, ConvDesc, PaiError  # noqa: F401
+from .lib import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_SILU, ACT_TANH, BF16, F32, U8, ConvDesc, PaiError  # noqa: F401
 
 
 def code_of(dtype: torch.dtype) -> int:
@@ -1101,3 +1101,46 @@ def batch_gather(cache_a, cache_b, indices, count: int, table, out_a, out_b):
     L.check(L.load().pai_batch_gather(U8 if u8 else F32, _p(cache_a), _p(cache_b), M, per, _p(indices, torch.int64), int(count),
                                       _p(table, torch.float32) if u8 else None, _p(out_a, torch.float32),
                                       _p(out_b, torch.float32), _stream()), "pai_batch_gather")
+
+
+# ---- Palette sampling (models/palette.py, models/guided_diffusion/unet.py) ---------------------------------------
+def sattn_fwd(dtype, qkv, N, T, heads, ch, out):
+    """out [N][T][heads * ch] = QKVAttentionLegacy(qkv [N][T][heads * 3 * ch]) without the T x T scores (pai_sattn_fwd)."""
+    L.check(L.load().pai_sattn_fwd(code_of(dtype), _p(qkv, dtype), int(N), int(T), int(heads), int(ch), _p(out, dtype),
+                                   _stream()), "pai_sattn_fwd")
+
+
+def affine_act(dtype, x, rows_per_sample, N, C_, A, B, per_sample, act, out):
+    """out = act(x * A + B) on [N][rows][C]; A, B fp32 [C] or (per_sample) [N][C]; act none | SiLU (pai_affine_act)."""
+    if A.numel() != (N * C_ if per_sample else C_) or B.numel() != A.numel():
+        raise PaiError("affine_act: coefficient tensors do not match [N][C] / [C]")
+    L.check(L.load().pai_affine_act(code_of(dtype), _p(x, dtype), int(rows_per_sample), int(N), int(C_), _p(A, torch.float32),
+                                    _p(B, torch.float32), int(bool(per_sample)), int(act), _p(out, dtype), _stream()),
+            "pai_affine_act")
+
+
+def film_coeffs(C_, N, a, b, emb_out, ld, A, B):
+    """A = a (1 + scale), B = b (1 + scale) + shift per sample; scale | shift = columns [0, C) | [C, 2C) of the rows of
+    ``emb_out`` (row stride ``ld`` elements) (pai_film_coeffs)."""
+    L.check(L.load().pai_film_coeffs(code_of(emb_out.dtype), int(C_), int(N), _p(a, torch.float32), _p(b, torch.float32),
+                                     _p(emb_out), int(ld), _p(A, torch.float32), _p(B, torch.float32), _stream()),
+            "pai_film_coeffs")
+
+
+def avgpool2(dtype, x, N, H, W, C_, out):
+    L.check(L.load().pai_avgpool2(code_of(dtype), _p(x, dtype), N, H, W, C_, _p(out, dtype), _stream()), "pai_avgpool2")
+
+
+def gamma_embedding(gammas, N, dim, out):
+    """out [N][dim] (fp32 or bf16) = [cos(g f) | sin(g f)] of the fp32 noise levels ``gammas`` (pai_gamma_embedding)."""
+    L.check(L.load().pai_gamma_embedding(code_of(out.dtype), _p(gammas, torch.float32), int(N), int(dim), _p(out), _stream()),
+            "pai_gamma_embedding")
+
+
+def palette_step(dtype, model_out, y_t, noise, pixels, C_, learn_var, add_noise, scalars, y_next, xy_next=None):
+    """One reverse diffusion step (pai_palette_step); ``scalars`` = (sqrt(1 - gamma), 1 / sqrt(gamma), the two mean
+    coefficients, log(var_lower), log(var_upper)) of the step as Python floats."""
+    s1, rs, c0, c1, llo, lhi = (float(v) for v in scalars)
+    L.check(L.load().pai_palette_step(code_of(dtype), _p(model_out, dtype), _p(y_t, torch.float32), _p(noise, torch.float32),
+                                      int(pixels), int(C_), int(bool(learn_var)), int(bool(add_noise)), s1, rs, c0, c1, llo,
+                                      lhi, _p(y_next, torch.float32), _p(xy_next, dtype), _stream()), "pai_palette_step")
