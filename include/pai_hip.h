@@ -60,7 +60,8 @@ const char* pai_last_error(void);
  * layers with more than 2048 partial rows (callers that size the buffer through it need no change).
  * 133: device-resident data set (pai_resize_aa_u8, pai_batch_gather, pai_data_kernel_name), PAI_U8.
  * 134: report evaluation (pai_eval_planes, pai_eval_kernel_name).
- * 135: Palette sampling (pai_sattn_fwd, pai_affine_act, pai_film_coeffs, pai_avgpool2, pai_gamma_embedding, pai_palette_step), PAI_ACT_SILU. */
+ * 135: Palette sampling (pai_sattn_fwd, pai_affine_act, pai_film_coeffs, pai_avgpool2, pai_gamma_embedding, pai_palette_step), PAI_ACT_SILU.
+ * 136: pai_mha_kernel_name. */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -446,6 +447,11 @@ int pai_instnorm_bwd(int dtype, const void* g, const void* x, int N, int HW, int
  *                       mask (fp32, shaped like probs, 0 or 1 / (1 - p); NULL = none): the Dropout on the attention
  *                       weights, out = (softmax(..) * mask) v; drawing it is the caller's RNG plumbing.
  *                       batch_first = False in the reference: S is the IMAGE batch, B the patch count.
+ *   pai_mha_kernel_name symbol of the kernel behind pai_mha_fwd (op 0) / pai_mha_bwd (op 1) at this dtype, S and head
+ *                       dim, as pai_conv_kernel_name: "mha_fwd_mfma_k" / "mha_bwd_mfma_k" on the matrix cores (bf16,
+ *                       S <= 32, hd a multiple of 32 up to 512, tunable mha_mfma != 0), else "mha_fwd_k<T>" and the pair
+ *                       "mha_bwd_q_k<T>+mha_bwd_kv_k<T>" (T = float / unsigned short).  Host only; the launchers branch
+ *                       on the same selection.  ABI 136.
  *   pai_subsample2      out[n][y][x][c] = x[n][2y][2x][c]; _bwd writes the zero-filled adjoint [N][H][W][C].
  *                       Conv2d(k3, s2, p1) = subsample(Conv2d(k3, s1, p1)), Conv2d(k1, s2) = Conv2d(k1)(subsample)
  *                       (EncoderBlock, :203-227).
@@ -466,6 +472,7 @@ int pai_mha_fwd(int dtype, const void* qkv, int S, int B, int heads, int hd, con
                 float* probs, void* stream);
 int pai_mha_bwd(int dtype, const void* dout, const void* qkv, const float* probs, int S, int B, int heads,
                 int hd, const float* mask, void* dqkv, float* ds_workspace, void* stream);
+int pai_mha_kernel_name(int dtype, int S, int hd, int op, char* name, int name_len);
 int pai_subsample2(int dtype, const void* x, int N, int H, int W, int C, void* out, void* stream);
 int pai_subsample2_bwd(int dtype, const void* dout, int N, int H, int W, int C, void* dx, void* stream);
 int pai_bn_stats_rows(int64_t M);

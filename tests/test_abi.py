@@ -118,3 +118,30 @@ def test_kernel_dispatch_table_without_gpu(pai):
     for layer, ((tr, N, H, C1, C2, Cout), want) in cfg2.items():
         d = ops.make_desc(torch.bfloat16, tr, N, H, H, C1, C2, Cout, 2, tr, tr if C2 else 0)
         assert tuple(ops.conv_kernel_name(d, op) for op in (0, 1, 2)) == want, layer
+
+
+def test_mha_kernel_selection_without_gpu(pai):
+    """Which attention kernels pai_mha_fwd / pai_mha_bwd launch is host logic (pai_mha_kernel_name reads the selection the
+    launchers branch on): the matrix cores for bf16, S <= 32, head dim a multiple of 32 up to 512, unless the tunable
+    mha_mfma is 0; the vector kernels of the storage type otherwise."""
+    import torch
+    from thesis_pai_reconstruction_amd import ops
+    bf, f32 = torch.bfloat16, torch.float32
+    mfma = ("mha_fwd_mfma_k", "mha_bwd_mfma_k")
+    vec = lambda t: (f"mha_fwd_k<{t}>", f"mha_bwd_q_k<{t}>+mha_bwd_kv_k<{t}>")
+    names = lambda dt, S, hd: (ops.mha_kernel_name(dt, S, hd, 0), ops.mha_kernel_name(dt, S, hd, 1))
+    for S, hd in ((1, 32), (7, 64), (32, 512)):
+        assert names(bf, S, hd) == mfma
+        assert names(f32, S, hd) == vec("float")
+    for S, hd in ((33, 32), (8, 48), (32, 544), (300, 24)):
+        assert names(bf, S, hd) == vec("unsigned short")
+    ops.set_tunable("mha_mfma", 0)
+    try:
+        assert names(bf, 32, 64) == vec("unsigned short")
+    finally:
+        ops.set_tunable("mha_mfma")
+    assert names(bf, 32, 64) == mfma
+    with pytest.raises(ops.PaiError, match="64 KB"):
+        ops.mha_kernel_name(f32, 8192, 64, 0)
+    with pytest.raises(ops.PaiError, match="op 2"):
+        ops.mha_kernel_name(bf, 8, 64, 2)

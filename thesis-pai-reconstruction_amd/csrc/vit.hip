@@ -584,6 +584,19 @@ static bool mha_mfma_ok(int dtype, int S, int hd) {
     return dtype == PAI_BF16 && S <= 32 && (hd % 32) == 0 && hd <= 512 && pai_tunable("mha_mfma", 1);
 }
 
+// ONE selection per call: the launchers branch on .mfma and pai_mha_kernel_name prints .fwd / .bwd of the same struct.
+struct MhaSel {
+    bool mfma;
+    const char* fwd;
+    const char* bwd;
+};
+
+static MhaSel mha_select(int dtype, int S, int hd) {
+    if (mha_mfma_ok(dtype, S, hd)) return {true, "mha_fwd_mfma_k", "mha_bwd_mfma_k"};
+    if (dtype == PAI_F32) return {false, "mha_fwd_k<float>", "mha_bwd_q_k<float>+mha_bwd_kv_k<float>"};
+    return {false, "mha_fwd_k<unsigned short>", "mha_bwd_q_k<unsigned short>+mha_bwd_kv_k<unsigned short>"};
+}
+
 static int mha_check(const char* who, int dtype, int S, int B, int heads, int hd) {
     PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "%s: bad dtype %d", who, dtype);
     PAI_CHECK(S > 0 && B > 0 && heads > 0 && hd > 0, "%s: bad shape S=%d B=%d heads=%d hd=%d", who, S, B, heads, hd);
@@ -600,7 +613,7 @@ extern "C" int pai_mha_fwd(int dtype, const void* qkv, int S, int B, int heads, 
     const float scale = 1.0f / sqrtf((float)hd);
     const size_t lds = (size_t)(hd + S + 16) * sizeof(float);
     const dim3 grid((unsigned)(S * B * heads));
-    if (mha_mfma_ok(dtype, S, hd)) {
+    if (mha_select(dtype, S, hd).mfma) {
         const size_t ml = (size_t)32 * hd * 2 + 4 * 32 * 33 * sizeof(float) + 32 * 32 * 2;
         static PerDeviceOnce attr;
         if (attr.first()) {
@@ -632,7 +645,7 @@ extern "C" int pai_mha_bwd(int dtype, const void* dout, const void* qkv, const f
     const float scale = 1.0f / sqrtf((float)hd);
     const size_t lds_q = (size_t)(hd + S + 16) * sizeof(float), lds_kv = (size_t)(2 * S) * sizeof(float);
     const dim3 grid((unsigned)(S * B * heads));
-    if (mha_mfma_ok(dtype, S, hd)) {
+    if (mha_select(dtype, S, hd).mfma) {
         const size_t ml = (size_t)3 * 32 * hd * 2 + 4 * 32 * 33 * sizeof(float) + 3 * 32 * 32 * 2;
         static PerDeviceOnce attr;
         if (attr.first()) {
@@ -656,6 +669,15 @@ extern "C" int pai_mha_bwd(int dtype, const void* dout, const void* qkv, const f
                            probs, ds_workspace, S, B, heads, hd, scale, (bf16_t*)dqkv, mask);
     }
     PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pai_mha_kernel_name(int dtype, int S, int hd, int op, char* name, int name_len) {
+    PAI_CHECK(name && name_len > 0, "pai_mha_kernel_name: bad arguments");
+    PAI_CHECK(op == 0 || op == 1, "pai_mha_kernel_name: op %d (0 forward, 1 backward)", op);
+    if (mha_check("pai_mha_kernel_name", dtype, S, 1, 1, hd)) return 1;
+    const MhaSel sel = mha_select(dtype, S, hd);
+    snprintf(name, (size_t)name_len, "%s", op == 0 ? sel.fwd : sel.bwd);
     return 0;
 }
 

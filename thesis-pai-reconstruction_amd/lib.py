@@ -125,6 +125,7 @@ SIGNATURES = {
     "pai_gelu_bwd": (_I, [_I, _P, _P, _L, _P, _P]),
     "pai_mha_fwd": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pai_mha_bwd": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "pai_mha_kernel_name": (_I, [_I, _I, _I, _I, C.c_char_p, _I]),
     "pai_subsample2": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
     "pai_subsample2_bwd": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
     "pai_bn_stats_rows": (_I, [_L]),

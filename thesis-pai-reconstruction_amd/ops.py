@@ -614,6 +614,15 @@ def mha_bwd(dtype, dout, qkv, probs, S, B, heads, hd, dqkv, ds_ws, mask=None):
                                  _p(mask, torch.float32), _p(dqkv), _p(ds_ws, torch.float32), _stream()), "pai_mha_bwd")
 
 
+def mha_kernel_name(dtype, S, hd, op: int = 0) -> str:
+    """rocprofv3 symbol of the kernel behind ``mha_fwd`` (op 0) / ``mha_bwd`` (op 1) at this dtype, S and head dim: the
+    selection the launchers branch on (host only)."""
+    buf = C.create_string_buffer(96)
+    if L.load().pai_mha_kernel_name(code_of(dtype), S, hd, op, buf, 96) != 0:
+        L.check(1, "pai_mha_kernel_name")
+    return buf.value.decode()
+
+
 def subsample2(dtype, x, N, H, W, C_, out):
     L.check(L.load().pai_subsample2(code_of(dtype), _p(x), N, H, W, C_, _p(out), _stream()), "pai_subsample2")
 
