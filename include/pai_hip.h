@@ -61,7 +61,9 @@ const char* pai_last_error(void);
  * 133: device-resident data set (pai_resize_aa_u8, pai_batch_gather, pai_data_kernel_name), PAI_U8.
  * 134: report evaluation (pai_eval_planes, pai_eval_kernel_name).
  * 135: Palette sampling (pai_sattn_fwd, pai_affine_act, pai_film_coeffs, pai_avgpool2, pai_gamma_embedding, pai_palette_step), PAI_ACT_SILU.
- * 136: pai_mha_kernel_name. */
+ * 136: pai_mha_kernel_name.
+ * 137: pai_denormalize and the fused `denorm` of the metric entry points keep a NaN (torch.clamp); they returned 0 for it;
+ * the multi-tensor calls (pai_adam_multi, pai_adam_multi_dev, pai_zero_multi, pai_lerp_multi) accept NULL for a tensor of 0 elements. */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -539,15 +541,17 @@ int pai_metrics_take(double* sums, int64_t n_images, int64_t numel, float* out3,
 int pai_tanh_bwd(int dtype, const float* pred, const float* g_a, const float* g_b, int64_t numel,
                  void* dh, void* stream);
 
-/* denormalize (models/utils.py:11): out = clamp(x*0.5+0.5, 0, 1).  With grad_out != NULL
- * the call computes the backward instead: out = grad_out * 0.5 where 0 <= x*0.5+0.5 <= 1. */
+/* denormalize (models/utils.py:11): out = clamp(x*0.5+0.5, 0, 1) as torch.clamp: a NaN stays a NaN (ABI 137; it became
+ * 0 before).  With grad_out != NULL the call computes the backward instead: out = grad_out * 0.5 where
+ * 0 <= x*0.5+0.5 <= 1 (boundaries included), 0 elsewhere and at a NaN. */
 int pai_denormalize(const float* x, const float* grad_out_or_null, int64_t numel, float* out,
                     void* stream);
 
 /* ---------------------------------------------------------------------------
  * Metrics.  Replace torchmetrics.functional SSIM / PSNR / MSE as called from
  * models/utils.py:38-47 and report.py:78-96 on denormalised images
- * (models/utils.py:11: clamp(x*0.5+0.5, 0, 1); `denorm` != 0 fuses it).
+ * (models/utils.py:11: clamp(x*0.5+0.5, 0, 1); `denorm` != 0 fuses it, a NaN pixel staying NaN as with `denorm` == 0, so
+ * that the sums of its image are NaN and never the metrics of a black pixel -- ABI 137).
  * All reductions accumulate (+=) in fp64; the caller zeroes them.
  * out2[0] += sum over images (N*C planes) of the per-plane 5-px-cropped SSIM mean
  * out2[1] += sum of squared error over all pixels
@@ -603,7 +607,8 @@ int pai_adam_dev(float* param, const float* grad, float* exp_avg, float* exp_avg
                  float lr, float beta1, float beta2, float eps, int64_t* step_dev, float* coeff2_dev, void* stream);
 /* The same update over `count` separately allocated fp32 tensors (HOST arrays of device pointers and element
  * counts), a few launches in all: the optimizer of the composable networks (models/res_unet.py, models/trans_unet.py),
- * whose parameters are not one arena. */
+ * whose parameters are not one arena.  A tensor of 0 elements may have NULL pointers (torch hands NULL for an empty
+ * tensor) and is skipped -- ABI 137, also in pai_adam_multi_dev, pai_zero_multi and pai_lerp_multi; it was an error. */
 int pai_adam_multi(int count, void* const* params, const void* const* grads, void* const* exp_avgs,
                    void* const* exp_avg_sqs, const int64_t* numels, float lr, float beta1, float beta2, float eps,
                    int step_count, void* stream);

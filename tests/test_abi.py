@@ -145,3 +145,12 @@ def test_mha_kernel_selection_without_gpu(pai):
         ops.mha_kernel_name(f32, 8192, 64, 0)
     with pytest.raises(ops.PaiError, match="op 2"):
         ops.mha_kernel_name(bf, 8, 64, 2)
+
+
+def test_version_is_the_last_one_the_header_lists(pai):
+    """The ABI history in front of pai_version() ("100: ... 137: ...") ends at the number the library reports: a change of
+    the contract text bumps both."""
+    src = open(HEADER).read()
+    block = src[src.index("/* 100: round 1."):src.index("int pai_version(void);")]
+    listed = [int(n) for n in re.findall(r"(?m)^(?:/\*| \*) (\d{3}):", block)]
+    assert listed == sorted(listed) and listed[-1] == pai.lib.load().pai_version(), listed

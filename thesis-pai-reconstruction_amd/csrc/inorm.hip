@@ -3,9 +3,15 @@
 // `norm=True`; the reference's own Discriminator never enables it).
 //   forward   y = act((x - mean[n][c]) * rstd[n][c]),  mean / biased variance over the H x W pixels of sample n
 //   backward  du = g * act'(y);  dx = rstd * (du - mean(du) - xhat * mean(du * xhat)),  xhat rebuilt from x
-// One workgroup = one sample x 64 channels: 8 chunk lanes x 32 pixel lanes sweep the sample twice (statistics, then the
-// normalisation; the second sweep comes from L2 for the sizes a discriminator sees).  Sums in fp32 per lane (<= HW / 32
-// terms), fp64 across the lanes.
+// One workgroup = one sample x 64 channels: 8 chunk lanes x 32 pixel lanes sweep the sample (the forward three times: two
+// for the statistics, one for the normalisation; the later sweeps come from L2 for the sizes a discriminator sees).  Sums
+// in fp32 per lane (<= HW / 32 terms), fp64 across the lanes.  The forward statistics are those of x - pivot (the shifted
+// one-pass variance), swept twice: pivot = the channel's first pixel of the sample, then pivot = the fp32 mean that sweep
+// found.  The plain E[x^2] - E[x]^2 lost a constant plane of 3.3 to the rounding of its own lane sums (mean off by 18 ulp,
+// rstd 148 for 316, y = 5e-4 for 0); with the first pixel as pivot that plane is exact (every difference is 0).  The first
+// pixel alone is a poor pivot when it is an outlier -- the sums of x - pivot then have the condition number
+// 1 + ((pivot - mean) / sigma)^2, and a first pixel 100 sigma off missed 1e-5 of mean |x| at HW = 4096 -- so its mean only
+// serves as the second pivot, which lies within that error of the true mean: condition number 1 for any plane.
 #include "common.h"
 
 namespace {
@@ -28,6 +34,14 @@ __device__ __forceinline__ void in_block_sums(double (*red)[32][64], const float
 #pragma unroll
     for (int e = 0; e < 8; ++e) { o1[e] = (float)red[0][0][cl * 8 + e]; o2[e] = (float)red[1][0][cl * 8 + e]; }
 }
+
+// du = g * act'(xhat), rounded ONCE, the same number in both sweeps of the backward kernel: contracted into the
+// subtraction of the second sweep (fma(g, slope, -mean(du))) it was the unrounded product there and the rounded one in the
+// sums, and a plane of one pixel (dx = 0 exactly) came back as rstd = 316 times that rounding residue, 4e-6.
+__device__ __forceinline__ float in_du(float g, float xh, int act) {
+#pragma clang fp contract(off)
+    return g * act_grad(xh, act);
+}
 }  // namespace
 
 template <typename T>
@@ -39,26 +53,40 @@ __global__ __launch_bounds__(256) void instnorm_fwd_k(const T* x, int HW, int C,
     const bool cv = c0 + cl * 8 < C;
     const T* xs = x + (size_t)n * HW * C + c0 + cl * 8;
     T* ys = y + (size_t)n * HW * C + c0 + cl * 8;
-    float s1[8], s2[8];
+    float s1[8], s2[8], pv[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
-    if (cv)
-        for (int p = pl; p < HW; p += 32) {
-            float v[8];
-            V8<T>::ld(xs + (size_t)p * C, v);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { s1[e] += v[e]; s2[e] = fmaf(v[e], v[e], s2[e]); }
-        }
+    for (int e = 0; e < 8; ++e) s1[e] = s2[e] = pv[e] = 0.f;
+    if (cv) V8<T>::ld(xs, pv);      // the first pivot: pixel 0 of this sample
     float t1[8], t2[8];
-    in_block_sums(red, s1, s2, pl, cl, t1, t2);
+    for (int sweep = 0; sweep < 2; ++sweep) {
+        if (cv)
+            for (int p = pl; p < HW; p += 32) {
+                float v[8];
+                V8<T>::ld(xs + (size_t)p * C, v);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float d = v[e] - pv[e];
+                    s1[e] += d;
+                    s2[e] = fmaf(d, d, s2[e]);
+                }
+            }
+        in_block_sums(red, s1, s2, pl, cl, t1, t2);
+        if (sweep) break;
+        __syncthreads();            // every lane has read the totals before `red` is filled again
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {   // the second pivot: the mean of the first sweep, as an fp32 number
+            pv[e] = (float)((double)pv[e] + (double)t1[e] / HW);
+            s1[e] = s2[e] = 0.f;
+        }
+    }
     if (!cv) return;
     float mu[8], rs[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const double m = (double)t1[e] / HW;
+        const double m = (double)t1[e] / HW;             // mean of x - pivot
         double var = (double)t2[e] / HW - m * m;
         if (var < 0.0) var = 0.0;
-        mu[e] = (float)m;
+        mu[e] = (float)((double)pv[e] + m);
         rs[e] = (float)(1.0 / sqrt(var + (double)eps));
     }
     if (pl == 0) {
@@ -100,7 +128,7 @@ __global__ __launch_bounds__(256) void instnorm_bwd_k(const T* g, const T* x, in
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float xh = (xv[e] - mu[e]) * rs[e];
-                const float du = gv[e] * act_grad(xh, act);       // sign(act(xhat)) = sign(xhat)
+                const float du = in_du(gv[e], xh, act);           // sign(act(xhat)) = sign(xhat)
                 s1[e] += du;
                 s2[e] = fmaf(du, xh, s2[e]);
             }
@@ -116,7 +144,7 @@ __global__ __launch_bounds__(256) void instnorm_bwd_k(const T* g, const T* x, in
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float xh = (xv[e] - mu[e]) * rs[e];
-            const float du = gv[e] * act_grad(xh, act);
+            const float du = in_du(gv[e], xh, act);
             gv[e] = rs[e] * (du - t1[e] * inv - xh * t2[e] * inv);
         }
         V8<T>::st(dx + base + (size_t)p * C, gv);

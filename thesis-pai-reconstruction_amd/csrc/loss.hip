@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void denorm_k(const float* x, const float* g, 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < numel; i += (int64_t)gridDim.x * 256) {
         const float u = x[i] * 0.5f + 0.5f;
         if (g) out[i] = (u >= 0.f && u <= 1.f) ? 0.5f * g[i] : 0.f;
-        else out[i] = fminf(fmaxf(u, 0.f), 1.f);
+        else out[i] = u != u ? u : fminf(fmaxf(u, 0.f), 1.f);     // a NaN stays a NaN (torch.clamp), fmaxf(NaN, 0) is 0
     }
 }
 

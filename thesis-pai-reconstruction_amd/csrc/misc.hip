@@ -545,7 +545,9 @@ extern "C" int pai_adam_multi_dev(int count, void* const* params, const void* co
         memset(&c, 0, sizeof(c));
         int64_t big = 1;
         for (int i = 0; i < nt; ++i) {
-            PAI_CHECK(params[i0 + i] && grads[i0 + i] && exp_avgs[i0 + i] && exp_avg_sqs[i0 + i] && numels[i0 + i] >= 0,
+            // an empty tensor has no address (torch hands NULL for numel 0) and no work
+            PAI_CHECK(numels[i0 + i] == 0 ||
+                          (params[i0 + i] && grads[i0 + i] && exp_avgs[i0 + i] && exp_avg_sqs[i0 + i] && numels[i0 + i] > 0),
                       "pai_adam_multi_dev: null tensor %d", i0 + i);
             c.p[i] = (float*)params[i0 + i];
             c.g[i] = (const float*)grads[i0 + i];
@@ -576,7 +578,8 @@ extern "C" int pai_adam_multi(int count, void* const* params, const void* const*
         memset(&c, 0, sizeof(c));
         int64_t big = 1;
         for (int i = 0; i < nt; ++i) {
-            PAI_CHECK(params[i0 + i] && grads[i0 + i] && exp_avgs[i0 + i] && exp_avg_sqs[i0 + i] && numels[i0 + i] >= 0,
+            PAI_CHECK(numels[i0 + i] == 0 ||
+                          (params[i0 + i] && grads[i0 + i] && exp_avgs[i0 + i] && exp_avg_sqs[i0 + i] && numels[i0 + i] > 0),
                       "pai_adam_multi: null tensor %d", i0 + i);
             c.p[i] = (float*)params[i0 + i];
             c.g[i] = (const float*)grads[i0 + i];
@@ -617,7 +620,7 @@ extern "C" int pai_zero_multi(int count, void* const* ptrs, const int64_t* numel
         memset(&c, 0, sizeof(c));
         int64_t big = 1;
         for (int i = 0; i < nt; ++i) {
-            PAI_CHECK(ptrs[i0 + i] && numels[i0 + i] >= 0, "pai_zero_multi: null tensor %d", i0 + i);
+            PAI_CHECK(numels[i0 + i] == 0 || (ptrs[i0 + i] && numels[i0 + i] > 0), "pai_zero_multi: null tensor %d", i0 + i);
             c.p[i] = (float*)ptrs[i0 + i];
             c.n[i] = numels[i0 + i];
             if (c.n[i] > big) big = c.n[i];
@@ -664,7 +667,7 @@ extern "C" int pai_lerp_multi(int count, void* const* dsts, const void* const* s
         memset(&c, 0, sizeof(c));
         int64_t big = 1;
         for (int i = 0; i < nt; ++i) {
-            PAI_CHECK(dsts[i0 + i] && srcs[i0 + i] && numels[i0 + i] >= 0, "pai_lerp_multi: null tensor %d", i0 + i);
+            PAI_CHECK(numels[i0 + i] == 0 || (dsts[i0 + i] && srcs[i0 + i] && numels[i0 + i] > 0), "pai_lerp_multi: null tensor %d", i0 + i);
             c.d[i] = (float*)dsts[i0 + i];
             c.s[i] = (const float*)srcs[i0 + i];
             c.n[i] = numels[i0 + i];

@@ -37,8 +37,12 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
     return min(max(i, 0), n - 1);
 }
 
+// clamp(u, 0, 1) as torch.clamp: a NaN stays a NaN (fmaxf(NaN, 0) = 0 would launder a diverged prediction into a black
+// pixel and the metrics into finite numbers -- the ReLU epilogues of the convolutions had the same fault, common.h act_fwd)
 __device__ __forceinline__ float denorm_val(float v, int denorm) {
-    return denorm ? fminf(fmaxf(v * 0.5f + 0.5f, 0.f), 1.f) : v;
+    if (!denorm) return v;
+    const float u = v * 0.5f + 0.5f;
+    return u != u ? u : fminf(fmaxf(u, 0.f), 1.f);
 }
 
 __device__ __forceinline__ void block_add2(double a, double b, double* da, double* db, double* dc) {
