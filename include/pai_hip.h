@@ -63,7 +63,8 @@ const char* pai_last_error(void);
  * 135: Palette sampling (pai_sattn_fwd, pai_affine_act, pai_film_coeffs, pai_avgpool2, pai_gamma_embedding, pai_palette_step), PAI_ACT_SILU.
  * 136: pai_mha_kernel_name.
  * 137: pai_denormalize and the fused `denorm` of the metric entry points keep a NaN (torch.clamp); they returned 0 for it;
- * the multi-tensor calls (pai_adam_multi, pai_adam_multi_dev, pai_zero_multi, pai_lerp_multi) accept NULL for a tensor of 0 elements. */
+ * the multi-tensor calls (pai_adam_multi, pai_adam_multi_dev, pai_zero_multi, pai_lerp_multi) accept NULL for a tensor of 0 elements.
+ * 138: differentiable spatial attention (pai_sattn_fwd_lse, pai_sattn_bwd, pai_sattn_kernel_name). */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -736,7 +737,8 @@ int pai_data_kernel_name(int op, int src_dtype, char* name, int name_len);
 
 /* ---------------------------------------------------------------------------
  * Palette sampling: the eval-mode guided-diffusion U-Net and the reverse diffusion step (reference models/palette.py:79-100,
- * 233-306, models/guided_diffusion/unet.py, nn.py).  Forward only.  Tensors are 16-byte aligned.
+ * 233-306, models/guided_diffusion/unet.py, nn.py).  Forward only, except the attention (pai_sattn_bwd).  Tensors are
+ * 16-byte aligned.
  *
  * pai_sattn_fwd: QKVAttentionLegacy (unet.py:265-297) over the T tokens of a level.  qkv [N][T][heads * 3 * ch] is the NHWC
  * output of the 1 x 1 qkv convolution in the reference's channel order [head][q | k | v][ch]; out [N][T][heads * ch], head h
@@ -745,6 +747,19 @@ int pai_data_kernel_name(int op, int src_dtype, char* name, int name_len);
  * rescaled at every key tile.  ch in {32, 64, 128, 256}, any other value is refused; T >= 1, a key tail that is not a whole
  * tile is masked, not read.  PAI_BF16: both products on the matrix cores, the probabilities and the output each rounded
  * once to bf16.  PAI_F32: exact fp32 FMA chains (the parity mode).
+ * pai_sattn_fwd_lse (ABI 138): the same kernels and the same out bits; additionally lse (fp32) [N][heads][T] = m + ln(l), the
+ * natural-log sum-exp of the scaled scores scale2 q.k of query t, scale2 = ch ** -0.5.
+ * pai_sattn_bwd (ABI 138): the backward on the tensors it is handed, the T x T scores never stored.  dout, out
+ * [N][T][heads * ch]; dqkv in qkv's layout [N][T][heads][dq | dk | dv][ch]; ws fp32 [N * heads * T] receives
+ * delta_i = sum_c dO_ic O_ic.  P_ij = exp(scale2 s_ij - lse_i) (one difference before the exp), dP_ij = dO_i . V_j,
+ * dS_ij = P_ij (dP_ij - delta_i), dV_j = sum_i P_ij dO_i, dK_j = scale2 sum_i dS_ij Q_i, dQ_i = scale2 sum_j dS_ij K_j.  Three
+ * launches (delta; dK / dV with the key on the lane; dQ with the query on the lane), no atomics and no sum across
+ * workgroups: the same bits on every run.  Every element of dqkv is written; nothing else but ws is.  PAI_F32: ch in
+ * {32, 64, 128, 256}, vector-ALU FMA chains.  PAI_BF16: ch in {32, 64, 128} on the matrix cores, P and dS each rounded once to
+ * bf16; ch = 256 is refused before any launch.
+ * pai_sattn_kernel_name (ABI 138): symbol(s) of the kernels behind pai_sattn_fwd / _fwd_lse (op 0) and pai_sattn_bwd (op 1,
+ * the three launches joined by '+') at this dtype and ch, as pai_mha_kernel_name.  Host only; the launchers branch on the
+ * same selection.
  * pai_affine_act: out = act(x * A + B) on [N][rows_per_sample][C], C a multiple of 8 and at most 2048; A, B fp32 [C]
  * (per_sample = 0) or [N][C] (per_sample = 1); act PAI_ACT_NONE | PAI_ACT_SILU.  Every BatchNorm (eval) + SiLU site of the
  * U-Net, with FiLM folded into per-sample coefficients, and the bare SiLU (A = 1, B = 0).  out may alias x.
@@ -760,6 +775,10 @@ int pai_data_kernel_name(int op, int src_dtype, char* name, int name_len);
  * y_next = mean + exp(log variance / 2) noise when add_noise, else mean.  xy_next (dtype, optional) [pixel][2 C]: the columns
  * C .. 2 C - 1 get y_next -- the y half of the [x | y_t] tensor the next U-Net call reads.  y_next may alias y_t. */
 int pai_sattn_fwd(int dtype, const void* qkv, int N, int T, int heads, int ch, void* out, void* stream);
+int pai_sattn_fwd_lse(int dtype, const void* qkv, int N, int T, int heads, int ch, void* out, float* lse, void* stream);
+int pai_sattn_bwd(int dtype, const void* dout, const void* qkv, const void* out, const float* lse, int N, int T, int heads,
+                  int ch, void* dqkv, float* ws, void* stream);
+int pai_sattn_kernel_name(int dtype, int ch, int op, char* name, int name_len);
 int pai_affine_act(int dtype, const void* x, int64_t rows_per_sample, int N, int C, const float* A, const float* B,
                    int per_sample, int act, void* out, void* stream);
 int pai_film_coeffs(int dtype, int C, int N, const float* a, const float* b, const void* emb_out, int64_t ld, float* A,

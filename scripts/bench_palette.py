@@ -1,5 +1,7 @@
 """Palette sampling on one GPU: images/s and ms per U-Net forward of ``pai.Palette.forward``, and ``pai_sattn_fwd`` alone
-beside ``torch.nn.functional.scaled_dot_product_attention`` on the same data (both as TFLOP/s of 4 N heads T^2 ch).
+beside ``torch.nn.functional.scaled_dot_product_attention`` on the same data (both as TFLOP/s of 4 N heads T^2 ch), then
+``pai_sattn_bwd`` (its three launches) beside the backward of the same SDPA call (both as TFLOP/s of the algorithmic
+10 N heads T^2 ch; the kernels recompute S and execute 14).
 Random normal data throughout (never zeros: MI355X_MICROARCH, data-dependent power).  One JSON line per measurement.
 
     python scripts/bench_palette.py [--precision bf16-mixed] [--batch 8] [--size 256] [--steps 100] [--mults 1,1,2,2,4,4]
@@ -55,6 +57,30 @@ def bench_attention(dtype, n, heads):
         except RuntimeError as e:           # e.g. the materialised form running out of memory at T = 16384
             row.update(sdpa_ms=None, sdpa_error=str(e).splitlines()[0][:120])
         print(json.dumps(row), flush=True)
+        bench_attention_bwd(dtype, n, heads, T, ch, qkv, iters)
+
+
+def bench_attention_bwd(dtype, n, heads, T, ch, qkv, iters):
+    out = torch.empty(n, T, heads * ch, dtype=dtype, device="cuda")
+    lse = torch.empty(n, heads, T, device="cuda")
+    ops.sattn_fwd_lse(dtype, qkv, n, T, heads, ch, out, lse)
+    dout = torch.randn(n, T, heads * ch, device="cuda").to(dtype)
+    dqkv, ws = torch.empty_like(qkv), torch.empty(n * heads * T, device="cuda")
+    flop = 10.0 * n * heads * T * T * ch
+    ms = timed(lambda: ops.sattn_bwd(dtype, dout, qkv, out, lse, n, T, heads, ch, dqkv, ws), 2, iters)
+    row = {"bench": "sattn_bwd", "dtype": str(dtype), "N": n, "heads": heads, "T": T, "ch": ch, "ms": round(ms, 4),
+           "tflops": round(flop / ms / 1e9, 2)}
+    try:
+        q, k, v = (t.permute(0, 2, 1, 3).detach().requires_grad_(True) for t in qkv.view(n, T, heads, 3, ch).unbind(3))
+        o = torch.nn.functional.scaled_dot_product_attention(q, k, v)
+        do = dout.view(n, T, heads, ch).permute(0, 2, 1, 3)
+        sd = timed(lambda: torch.autograd.grad(o, (q, k, v), do, retain_graph=True), 2, iters)
+        ref = torch.stack(torch.autograd.grad(o, (q, k, v), do), 3).permute(0, 2, 1, 3, 4).reshape(n, T, heads * 3 * ch)
+        row.update(sdpa_ms=round(sd, 4), sdpa_tflops=round(flop / sd / 1e9, 2),
+                   max_diff=float((ref.float() - dqkv.float()).abs().max()))
+    except RuntimeError as e:
+        row.update(sdpa_ms=None, sdpa_error=str(e).splitlines()[0][:120])
+    print(json.dumps(row), flush=True)
 
 
 def main():

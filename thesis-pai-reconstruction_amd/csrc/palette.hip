@@ -1,5 +1,5 @@
 // Palette sampling (reference models/palette.py:79-100,233-306 and models/guided_diffusion/unet.py, nn.py): the kernels the
-// eval-mode guided-diffusion U-Net and the reverse step need beside the convolution family.
+// eval-mode guided-diffusion U-Net and the reverse step need beside the convolution family, and the attention's backward.
 //
 //   pai_sattn_fwd        QKVAttentionLegacy (unet.py:265-297) over the T = H * W tokens of a level, flash style: the T x T
 //                        scores are never stored.  bf16: one workgroup of four waves per 128 queries of one (image, head),
@@ -12,6 +12,9 @@
 //                        row-major LDS image through ds_read_b64_tr_b16 in the k order the accumulator imposes.  The
 //                        rescale happens at every tile (no deferred maximum).  fp32 (parity mode): a vector-ALU kernel with
 //                        the same online softmax, sequential FMA chains.
+//   pai_sattn_fwd_lse    the same kernels with the lse output (natural-log sum-exp of every query's scaled scores).
+//   pai_sattn_bwd        its backward from qkv, out, lse and dout in three launches (delta; dK / dV, key on the lane; dQ, query
+//                        on the lane), no sum across workgroups: in front of the kernels below.
 //   pai_affine_act       out = act(x * A + B), A / B per channel or per (sample, channel): every BatchNorm (eval) + SiLU
 //                        site of the network, FiLM included.
 //   pai_film_coeffs      A = a (1 + scale), B = b (1 + scale) + shift from the BatchNorm eval coefficients and emb_out.
@@ -62,7 +65,8 @@ __device__ __forceinline__ pbf8_t sattn_vt_frag(const bf16_t* Vs, int R0, int d0
 }
 
 template <int CH>
-__global__ __launch_bounds__(256) void sattn_bf16_k(const bf16_t* qkv, int T, int heads, float scale2, bf16_t* out) {
+__global__ __launch_bounds__(256) void sattn_bf16_k(const bf16_t* qkv, int T, int heads, float scale2, bf16_t* out,
+                                                    float* lse) {
     constexpr int KVB = CH > 128 ? 32 : 64;       // keys per tile
     constexpr int NS = KVB / 32;                  // 32-key sub-tiles
     constexpr int CPR = CH / 8;                   // 16-byte chunks per row
@@ -163,6 +167,7 @@ __global__ __launch_bounds__(256) void sattn_bf16_k(const bf16_t* qkv, int T, in
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.0f / l;
     if (qi < T) {
+        if (lse && hh == 0) lse[(int64_t)blockIdx.y * T + qi] = m + logf(l);      // [n][h][t], natural log
         bf16_t* orow = out + ((int64_t)n * T + qi) * heads * CH + (int64_t)h * CH;
 #pragma unroll
         for (int d = 0; d < DB; ++d)
@@ -180,7 +185,7 @@ __global__ __launch_bounds__(256) void sattn_bf16_k(const bf16_t* qkv, int T, in
 // 32 queries per workgroup, eight threads per query: each takes every eighth key of the tile for the scores and a slice of
 // the channels for the output.  Sequential FMA chains over the channels (scores) and over the keys (output).
 template <int CH, int KVB>
-__global__ __launch_bounds__(256) void sattn_f32_k(const float* qkv, int T, int heads, float scale2, float* out) {
+__global__ __launch_bounds__(256) void sattn_f32_k(const float* qkv, int T, int heads, float scale2, float* out, float* lse) {
     constexpr int NE = KVB / 8, ND = CH / 32;
     __shared__ __attribute__((aligned(16))) float Ks[KVB * CH];
     __shared__ __attribute__((aligned(16))) float Vs[KVB * CH];
@@ -264,45 +269,508 @@ __global__ __launch_bounds__(256) void sattn_f32_k(const float* qkv, int T, int 
     if (qi < T) {
         float* orow = out + ((int64_t)n * T + qi) * heads * CH + (int64_t)h * CH;
         const float inv = 1.0f / l;
+        if (lse && g == 0) lse[(int64_t)blockIdx.y * T + qi] = m + logf(l);
 #pragma unroll
         for (int e = 0; e < ND; ++e)
             *(float4*)(orow + 4 * g + 32 * e) = make_float4(o[e].x * inv, o[e].y * inv, o[e].z * inv, o[e].w * inv);
     }
 }
 
-extern "C" int pai_sattn_fwd(int dtype, const void* qkv, int N, int T, int heads, int ch, void* out, void* stream) {
-    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_sattn_fwd: dtype=%d", dtype);
-    PAI_CHECK(qkv && out, "pai_sattn_fwd: null tensor");
-    PAI_CHECK(N >= 1 && T >= 1 && heads >= 1, "pai_sattn_fwd: N=%d T=%d heads=%d", N, T, heads);
-    PAI_CHECK(ch == 32 || ch == 64 || ch == 128 || ch == 256, "pai_sattn_fwd: ch=%d (32, 64, 128 or 256 channels per head)", ch);
-    PAI_CHECK((int64_t)N * heads <= 65535, "pai_sattn_fwd: N * heads = %lld (at most 65535)", (long long)N * heads);
-    PAI_CHECK((((uintptr_t)qkv) | ((uintptr_t)out)) % 16 == 0, "pai_sattn_fwd: tensors must be 16-byte aligned");
+// ---- spatial self-attention, backward ------------------------------------------------------------------------------------
+// Three launches, none of which adds across workgroups: no atomics, no hand-off.  P is recomputed from q, k and the forward's
+// lse (P_ij = exp(scale2 s_ij - lse_i), the exponent one difference), so S is computed twice -- once per kernel below.
+//   delta     ws[n][h][i] = sum_c dO_ic O_ic, a streaming row dot.
+//   kv        one workgroup per 128 keys of one (image, head), a wave per 32 keys: key on the lane.  K and V fragments stay in
+//             registers as B operands; S = Q K^T and dP = dO V^T take the Q / dO rows of a query tile from LDS (K swizzle) and
+//             have the key on the lane and the queries in the 16 registers, so P and dS, rounded once to bf16, are the B
+//             operands of dV^T += dO^T P and dK^T += Q^T dS; dO^T / Q^T come through ds_read_b64_tr_b16 from a second LDS image
+//             (V swizzle) in the k order the accumulator imposes (sattn_vt_frag).  dK^T / dV^T stay in accumulators for the
+//             whole sweep over the queries.
+//   q         the forward's structure, query on the lane: S^T = K Q^T and dP^T = V dO^T with K / V rows from LDS and the
+//             Q / dO fragments in registers, dS^T rounded once to bf16 as the B operand of dQ^T += K^T dS^T, K^T through
+//             ds_read_b64_tr_b16 from a second image of K.
+// Queries (kv) and keys (q) past T are zero-filled in LDS and get P = 0 explicitly.
+template <typename T, int CH>
+__global__ __launch_bounds__(256) void sattn_bwd_delta_k(const T* dout, const T* out, int64_t rows, int Tn, int heads, float* ws) {
+    constexpr int L = CH / 8;                     // lanes per row
+    const int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = gi / L;                   // (n * Tn + t) * heads + h
+    const int sub = (int)(gi - row * L);
+    float acc = 0.f;
+    if (row < rows) {                             // the tail lanes add 0 and still take part in the shuffles below
+        float a[8], b[8];
+        V8<T>::ld(dout + row * CH + 8 * sub, a);
+        V8<T>::ld(out + row * CH + 8 * sub, b);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc = fmaf(a[i], b[i], acc);
+    }
+#pragma unroll
+    for (int o = 1; o < L; o <<= 1) acc += __shfl_xor(acc, o, 64);
+    if (row < rows && sub == 0) {
+        const int64_t nt = row / heads;
+        const int h = (int)(row - nt * heads);
+        const int64_t n = nt / Tn;
+        ws[(n * heads + h) * Tn + (nt - n * Tn)] = acc;
+    }
+}
+
+template <int CH>
+__global__ __launch_bounds__(256) void sattn_bwd_kv_bf16_k(const bf16_t* qkv, const bf16_t* dout, const float* lse,
+                                                           const float* delta, int T, int heads, float scale2, bf16_t* dqkv) {
+    constexpr int QB = CH > 64 ? 32 : 64;         // queries per tile
+    constexpr int NS = QB / 32;
+    constexpr int CPR = CH / 8;
+    constexpr int KS = CH / 16;
+    constexpr int DB = CH / 32;
+    __shared__ __attribute__((aligned(16))) bf16_t Qr[QB * CH];      // K swizzle: row reads
+    __shared__ __attribute__((aligned(16))) bf16_t Qt[QB * CH];      // V swizzle: transposed reads
+    __shared__ __attribute__((aligned(16))) bf16_t Dr[QB * CH];
+    __shared__ __attribute__((aligned(16))) bf16_t Dt[QB * CH];
+    __shared__ __attribute__((aligned(16))) float Ls[QB];
+    __shared__ __attribute__((aligned(16))) float Es[QB];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r = lane & 31, hh = lane >> 5;
+    const int n = blockIdx.y / heads, h = blockIdx.y - n * heads;
+    const int64_t RS = (int64_t)heads * 3 * CH, OS = (int64_t)heads * CH;
+    const bf16_t* base = qkv + (int64_t)n * T * RS + (int64_t)h * 3 * CH;
+    const bf16_t* dob = dout + (int64_t)n * T * OS + (int64_t)h * CH;
+    const float* lrow = lse + (int64_t)blockIdx.y * T;
+    const float* erow = delta + (int64_t)blockIdx.y * T;
+    const int kw0 = blockIdx.x * 128 + w * 32;
+    const bool active = kw0 < T;                  // wave-uniform
+    const int kj = kw0 + r;
+    const bool kvalid = kj < T;
+    const bf16_t* krow = base + (int64_t)min(kj, T - 1) * RS + CH;
+    pbf8_t kf[KS], vf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        kf[ks] = *(const pbf8_t*)(krow + 16 * ks + 8 * hh);
+        vf[ks] = *(const pbf8_t*)(krow + CH + 16 * ks + 8 * hh);
+    }
+    pf16_t dk[DB], dv[DB];
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) dk[d][t] = dv[d][t] = 0.f;
+
+    for (int q0 = 0; q0 < T; q0 += QB) {
+        __syncthreads();                          // the previous tile has been read
+        for (int c = tid; c < QB * CPR; c += 256) {
+            const int row = c / CPR, ch = c - row * CPR;
+            uint4 qv = make_uint4(0, 0, 0, 0), dv4 = make_uint4(0, 0, 0, 0);
+            if (q0 + row < T) {                   // the query tail is zero-filled, never read
+                qv = *(const uint4*)(base + (int64_t)(q0 + row) * RS + 8 * ch);
+                dv4 = *(const uint4*)(dob + (int64_t)(q0 + row) * OS + 8 * ch);
+            }
+            const int ok = row * CH + 8 * (ch ^ sattn_kswz<CH>(row)), ov = row * CH + 8 * (ch ^ sattn_vswz<CH>(row));
+            *(uint4*)(Qr + ok) = qv;
+            *(uint4*)(Qt + ov) = qv;
+            *(uint4*)(Dr + ok) = dv4;
+            *(uint4*)(Dt + ov) = dv4;
+        }
+        if (tid < QB) {
+            const bool in = q0 + tid < T;
+            Ls[tid] = in ? lrow[q0 + tid] : 0.f;
+            Es[tid] = in ? erow[q0 + tid] : 0.f;
+        }
+        __syncthreads();
+        if (!active) continue;
+#pragma unroll
+        for (int sb = 0; sb < NS; ++sb) {
+            // S = Q K^T and dP = dO V^T: D[row query][col key]; register t of lane (r, hh) is query 8 (t >> 2) + 4 hh + (t & 3)
+            pf16_t s, dp;
+#pragma unroll
+            for (int t = 0; t < 16; ++t) s[t] = dp[t] = 0.f;
+            const int qrow = 32 * sb + r;
+            const int qx = sattn_kswz<CH>(qrow);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const int off = qrow * CH + 8 * ((2 * ks + hh) ^ qx);
+                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const pbf8_t*)(Qr + off), kf[ks], s, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const pbf8_t*)(Dr + off), vf[ks], dp, 0, 0, 0);
+            }
+            pbf8_t pf[2], df[2];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int i0 = 32 * sb + 8 * g + 4 * hh;
+                const float4 l4 = *(const float4*)(Ls + i0), e4 = *(const float4*)(Es + i0);
+                const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, ev[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int t = 4 * g + u;
+                    // padded queries and padded keys contribute exactly zero
+                    const float p = (kvalid && q0 + i0 + u < T) ? __expf(fmaf(s[t], scale2, -lv[u])) : 0.f;
+                    const float ds = p * (dp[t] - ev[u]);
+                    pf[t >> 3][t & 7] = (__bf16)p;
+                    df[t >> 3][t & 7] = (__bf16)ds;
+                }
+            }
+            // dV^T += dO^T P, dK^T += Q^T dS: D[row channel][col key]
+#pragma unroll
+            for (int d = 0; d < DB; ++d)
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    dv[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sattn_vt_frag<CH>(Dt, 32 * sb + 16 * s2, 32 * d, lane), pf[s2],
+                                                                    dv[d], 0, 0, 0);
+                    dk[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sattn_vt_frag<CH>(Qt, 32 * sb + 16 * s2, 32 * d, lane), df[s2],
+                                                                    dk[d], 0, 0, 0);
+                }
+        }
+    }
+    if (!kvalid) return;
+    bf16_t* grow = dqkv + ((int64_t)n * T + kj) * RS + (int64_t)h * 3 * CH + CH;
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {             // registers 4g .. 4g + 3: channels 32 d + 8 g + 4 hh + (0 .. 3)
+            uint2 pk;
+            pk.x = pk2bf(dk[d][4 * g] * scale2, dk[d][4 * g + 1] * scale2);
+            pk.y = pk2bf(dk[d][4 * g + 2] * scale2, dk[d][4 * g + 3] * scale2);
+            *(uint2*)(grow + 32 * d + 8 * g + 4 * hh) = pk;
+            pk.x = pk2bf(dv[d][4 * g], dv[d][4 * g + 1]);
+            pk.y = pk2bf(dv[d][4 * g + 2], dv[d][4 * g + 3]);
+            *(uint2*)(grow + CH + 32 * d + 8 * g + 4 * hh) = pk;
+        }
+}
+
+template <int CH>
+__global__ __launch_bounds__(256) void sattn_bwd_q_bf16_k(const bf16_t* qkv, const bf16_t* dout, const float* lse,
+                                                          const float* delta, int T, int heads, float scale2, bf16_t* dqkv) {
+    constexpr int KVB = 64;                       // keys per tile
+    constexpr int NS = KVB / 32;
+    constexpr int CPR = CH / 8;
+    constexpr int KS = CH / 16;
+    constexpr int DB = CH / 32;
+    __shared__ __attribute__((aligned(16))) bf16_t Ks[KVB * CH];     // K swizzle: row reads
+    __shared__ __attribute__((aligned(16))) bf16_t Vs[KVB * CH];     // K swizzle: row reads
+    __shared__ __attribute__((aligned(16))) bf16_t Kt[KVB * CH];     // V swizzle: transposed reads
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r = lane & 31, hh = lane >> 5;
+    const int n = blockIdx.y / heads, h = blockIdx.y - n * heads;
+    const int64_t RS = (int64_t)heads * 3 * CH, OS = (int64_t)heads * CH;
+    const bf16_t* base = qkv + (int64_t)n * T * RS + (int64_t)h * 3 * CH;
+    const int q0 = blockIdx.x * 128 + w * 32;
+    const bool active = q0 < T;                   // wave-uniform
+    const int qi = q0 + r;
+    const int qc = min(qi, T - 1);
+    const bf16_t* qrow = base + (int64_t)qc * RS;
+    const bf16_t* drow = dout + ((int64_t)n * T + qc) * OS + (int64_t)h * CH;
+    pbf8_t qf[KS], dof[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        qf[ks] = *(const pbf8_t*)(qrow + 16 * ks + 8 * hh);
+        dof[ks] = *(const pbf8_t*)(drow + 16 * ks + 8 * hh);
+    }
+    const float lq = lse[(int64_t)blockIdx.y * T + qc], eq = delta[(int64_t)blockIdx.y * T + qc];
+    pf16_t dq[DB];
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) dq[d][t] = 0.f;
+
+    for (int k0 = 0; k0 < T; k0 += KVB) {
+        __syncthreads();                          // the previous tile has been read
+        for (int c = tid; c < KVB * CPR; c += 256) {
+            const int row = c / CPR, ch = c - row * CPR;
+            uint4 kv = make_uint4(0, 0, 0, 0), vv = make_uint4(0, 0, 0, 0);
+            if (k0 + row < T) {                   // the key tail is zero-filled, never read
+                const bf16_t* src = base + (int64_t)(k0 + row) * RS + CH + 8 * ch;
+                kv = *(const uint4*)src;
+                vv = *(const uint4*)(src + CH);
+            }
+            const int ok = row * CH + 8 * (ch ^ sattn_kswz<CH>(row));
+            *(uint4*)(Ks + ok) = kv;
+            *(uint4*)(Vs + ok) = vv;
+            *(uint4*)(Kt + row * CH + 8 * (ch ^ sattn_vswz<CH>(row))) = kv;
+        }
+        __syncthreads();
+        if (!active) continue;
+#pragma unroll
+        for (int sb = 0; sb < NS; ++sb) {
+            // S^T = K Q^T and dP^T = V dO^T: D[row key][col query]; register t of lane (r, hh) is key 8 (t >> 2) + 4 hh + (t & 3)
+            pf16_t s, dp;
+#pragma unroll
+            for (int t = 0; t < 16; ++t) s[t] = dp[t] = 0.f;
+            const int krow = 32 * sb + r;
+            const int kx = sattn_kswz<CH>(krow);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const int off = krow * CH + 8 * ((2 * ks + hh) ^ kx);
+                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const pbf8_t*)(Ks + off), qf[ks], s, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const pbf8_t*)(Vs + off), dof[ks], dp, 0, 0, 0);
+            }
+            pbf8_t df[2];
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const int key = k0 + 32 * sb + 8 * (t >> 2) + 4 * hh + (t & 3);
+                const float p = key < T ? __expf(fmaf(s[t], scale2, -lq)) : 0.f;       // keys past T: P = 0
+                df[t >> 3][t & 7] = (__bf16)(p * (dp[t] - eq));
+            }
+            // dQ^T += K^T dS^T: D[row channel][col query]
+#pragma unroll
+            for (int d = 0; d < DB; ++d)
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2)
+                    dq[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sattn_vt_frag<CH>(Kt, 32 * sb + 16 * s2, 32 * d, lane), df[s2],
+                                                                    dq[d], 0, 0, 0);
+        }
+    }
+    if (!active || qi >= T) return;
+    bf16_t* grow = dqkv + ((int64_t)n * T + qi) * RS + (int64_t)h * 3 * CH;
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {             // registers 4g .. 4g + 3: channels 32 d + 8 g + 4 hh + (0 .. 3)
+            uint2 pk;
+            pk.x = pk2bf(dq[d][4 * g] * scale2, dq[d][4 * g + 1] * scale2);
+            pk.y = pk2bf(dq[d][4 * g + 2] * scale2, dq[d][4 * g + 3] * scale2);
+            *(uint2*)(grow + 32 * d + 8 * g + 4 * hh) = pk;
+        }
+}
+
+// fp32 (parity mode): vector-ALU kernels, sequential FMA chains.  One kernel serves both sweeps: 32 "own" rows per workgroup
+// (queries for dQ, keys for dK / dV), eight threads per own row; each takes every eighth row of the "other" tile for the
+// scores and a slice of the channels for the gradients.
+//   KV = false: own = query i, other = key j:   dQ_i = scale2 sum_j dS_ij K_j
+//   KV = true:  own = key j, other = query i:   dK_j = scale2 sum_i dS_ij Q_i, dV_j = sum_i P_ij dO_i
+template <int CH, int OB, bool KV>
+__global__ __launch_bounds__(256) void sattn_bwd_f32_k(const float* qkv, const float* dout, const float* lse, const float* delta,
+                                                       int T, int heads, float scale2, float* dqkv) {
+    constexpr int NE = OB / 8, ND = CH / 32;
+    __shared__ __attribute__((aligned(16))) float As[OB * CH];       // other rows of S: K (dQ) or Q (dK / dV)
+    __shared__ __attribute__((aligned(16))) float Bs[OB * CH];       // other rows of dP: V (dQ) or dO (dK / dV)
+    __shared__ float Ps[32][OB + 1];
+    __shared__ float Ds[32][OB + 1];
+    const int tid = threadIdx.x, ol = tid >> 3, g = tid & 7;
+    const int n = blockIdx.y / heads, h = blockIdx.y - n * heads;
+    const int64_t RS = (int64_t)heads * 3 * CH, OS = (int64_t)heads * CH;
+    const float* base = qkv + (int64_t)n * T * RS + (int64_t)h * 3 * CH;
+    const float* dob = dout + (int64_t)n * T * OS + (int64_t)h * CH;
+    const float* lrow = lse + (int64_t)blockIdx.y * T;
+    const float* erow = delta + (int64_t)blockIdx.y * T;
+    const int oi = blockIdx.x * 32 + ol;
+    const int oc = min(oi, T - 1);
+    // the own row of S and of dP
+    const float* arow = base + (int64_t)oc * RS + (KV ? CH : 0);
+    const float* brow = KV ? base + (int64_t)oc * RS + 2 * CH : dob + (int64_t)oc * OS;
+    const float lo = KV ? 0.f : lrow[oc], eo = KV ? 0.f : erow[oc];
+    float4 ga[ND], gb[ND];                        // dQ or dK; dV
+#pragma unroll
+    for (int e = 0; e < ND; ++e) ga[e] = gb[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int t0 = 0; t0 < T; t0 += OB) {
+        __syncthreads();
+        for (int c = tid; c < OB * (CH / 4); c += 256) {
+            const int row = c / (CH / 4), c4 = c - row * (CH / 4);
+            float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av;
+            if (t0 + row < T) {
+                const float* src = base + (int64_t)(t0 + row) * RS + 4 * c4;
+                av = *(const float4*)(src + (KV ? 0 : CH));
+                bv = KV ? *(const float4*)(dob + (int64_t)(t0 + row) * OS + 4 * c4) : *(const float4*)(src + 2 * CH);
+            }
+            *(float4*)(As + row * CH + 4 * c4) = av;
+            *(float4*)(Bs + row * CH + 4 * c4) = bv;
+        }
+        __syncthreads();
+        float s[NE], dp[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) s[e] = dp[e] = 0.f;
+#pragma unroll 2                                  // a full unroll hoists the own rows out of the tile loop and spills
+        for (int c = 0; c < CH; c += 4) {
+            const float4 a = *(const float4*)(arow + c), b = *(const float4*)(brow + c);
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const float4 x = *(const float4*)(As + (g + 8 * e) * CH + c), y = *(const float4*)(Bs + (g + 8 * e) * CH + c);
+                s[e] = fmaf(a.x, x.x, s[e]);
+                s[e] = fmaf(a.y, x.y, s[e]);
+                s[e] = fmaf(a.z, x.z, s[e]);
+                s[e] = fmaf(a.w, x.w, s[e]);
+                dp[e] = fmaf(b.x, y.x, dp[e]);
+                dp[e] = fmaf(b.y, y.y, dp[e]);
+                dp[e] = fmaf(b.z, y.z, dp[e]);
+                dp[e] = fmaf(b.w, y.w, dp[e]);
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int ti = t0 + g + 8 * e;
+            const bool in = ti < T;               // padded rows of the other side: P = 0
+            const float li = KV ? (in ? lrow[ti] : 0.f) : lo, ei = KV ? (in ? erow[ti] : 0.f) : eo;
+            const float p = in ? expf(fmaf(s[e], scale2, -li)) : 0.f;
+            Ps[ol][g + 8 * e] = p;
+            Ds[ol][g + 8 * e] = p * (dp[e] - ei);
+        }
+        __syncthreads();
+        for (int k = 0; k < OB; ++k) {
+            const float ds = Ds[ol][k];
+#pragma unroll
+            for (int e = 0; e < ND; ++e) {
+                const float4 x = *(const float4*)(As + k * CH + 4 * g + 32 * e);
+                ga[e].x = fmaf(ds, x.x, ga[e].x);
+                ga[e].y = fmaf(ds, x.y, ga[e].y);
+                ga[e].z = fmaf(ds, x.z, ga[e].z);
+                ga[e].w = fmaf(ds, x.w, ga[e].w);
+            }
+            if (KV) {
+                const float p = Ps[ol][k];
+#pragma unroll
+                for (int e = 0; e < ND; ++e) {
+                    const float4 y = *(const float4*)(Bs + k * CH + 4 * g + 32 * e);
+                    gb[e].x = fmaf(p, y.x, gb[e].x);
+                    gb[e].y = fmaf(p, y.y, gb[e].y);
+                    gb[e].z = fmaf(p, y.z, gb[e].z);
+                    gb[e].w = fmaf(p, y.w, gb[e].w);
+                }
+            }
+        }
+    }
+    if (oi < T) {
+        float* grow = dqkv + ((int64_t)n * T + oi) * RS + (int64_t)h * 3 * CH + (KV ? CH : 0);
+#pragma unroll
+        for (int e = 0; e < ND; ++e) {
+            *(float4*)(grow + 4 * g + 32 * e) = make_float4(ga[e].x * scale2, ga[e].y * scale2, ga[e].z * scale2, ga[e].w * scale2);
+            if (KV) *(float4*)(grow + CH + 4 * g + 32 * e) = gb[e];
+        }
+    }
+}
+
+// ONE selection per call: the launchers branch on .idx / .bwd_ok and pai_sattn_kernel_name prints .fwd / .bwd of the same struct.
+struct SattnSel {
+    int idx;                                      // 0 .. 3: ch 32, 64, 128, 256; -1: no kernel
+    bool bwd_ok;
+    const char* fwd;
+    const char* bwd;
+};
+
+static SattnSel sattn_select(int dtype, int ch) {
+    static const char* const fwd_bf[4] = {"sattn_bf16_k<32>", "sattn_bf16_k<64>", "sattn_bf16_k<128>", "sattn_bf16_k<256>"};
+    static const char* const fwd_f[4] = {"sattn_f32_k<32, 32>", "sattn_f32_k<64, 32>", "sattn_f32_k<128, 32>", "sattn_f32_k<256, 16>"};
+    static const char* const bwd_bf[3] = {
+        "sattn_bwd_delta_k<unsigned short, 32>+sattn_bwd_kv_bf16_k<32>+sattn_bwd_q_bf16_k<32>",
+        "sattn_bwd_delta_k<unsigned short, 64>+sattn_bwd_kv_bf16_k<64>+sattn_bwd_q_bf16_k<64>",
+        "sattn_bwd_delta_k<unsigned short, 128>+sattn_bwd_kv_bf16_k<128>+sattn_bwd_q_bf16_k<128>"};
+    static const char* const bwd_f[4] = {
+        "sattn_bwd_delta_k<float, 32>+sattn_bwd_f32_k<32, 32, true>+sattn_bwd_f32_k<32, 32, false>",
+        "sattn_bwd_delta_k<float, 64>+sattn_bwd_f32_k<64, 32, true>+sattn_bwd_f32_k<64, 32, false>",
+        "sattn_bwd_delta_k<float, 128>+sattn_bwd_f32_k<128, 32, true>+sattn_bwd_f32_k<128, 32, false>",
+        "sattn_bwd_delta_k<float, 256>+sattn_bwd_f32_k<256, 16, true>+sattn_bwd_f32_k<256, 16, false>"};
+    const int idx = ch == 32 ? 0 : ch == 64 ? 1 : ch == 128 ? 2 : ch == 256 ? 3 : -1;
+    if (idx < 0) return {-1, false, "", ""};
+    if (dtype == PAI_BF16) return {idx, idx < 3, fwd_bf[idx], idx < 3 ? bwd_bf[idx] : ""};
+    return {idx, true, fwd_f[idx], bwd_f[idx]};
+}
+
+static int sattn_check(const char* who, int dtype, int N, int T, int heads, int ch) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "%s: dtype=%d", who, dtype);
+    PAI_CHECK(N >= 1 && T >= 1 && heads >= 1, "%s: N=%d T=%d heads=%d", who, N, T, heads);
+    PAI_CHECK(sattn_select(dtype, ch).idx >= 0, "%s: ch=%d (32, 64, 128 or 256 channels per head)", who, ch);
+    PAI_CHECK((int64_t)N * heads <= 65535, "%s: N * heads = %lld (at most 65535)", who, (long long)N * heads);
+    return 0;
+}
+
+static int sattn_forward(const char* who, int dtype, const void* qkv, int N, int T, int heads, int ch, void* out, float* lse,
+                         void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "%s: dtype=%d", who, dtype);
+    PAI_CHECK(qkv && out, "%s: null tensor", who);
+    if (sattn_check(who, dtype, N, T, heads, ch)) return 1;
+    PAI_CHECK((((uintptr_t)qkv) | ((uintptr_t)out)) % 16 == 0, "%s: tensors must be 16-byte aligned", who);
+    const SattnSel sel = sattn_select(dtype, ch);
     hipStream_t s = (hipStream_t)stream;
     const float scale2 = 1.0f / sqrtf((float)ch);           // (ch ** -0.25) ** 2
     if (dtype == PAI_BF16) {
         const dim3 grid(cdiv(T, 128), N * heads);
 #define PAI_SATTN_BF16(CH) \
-    hipLaunchKernelGGL((sattn_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, T, heads, scale2, (bf16_t*)out)
-        switch (ch) {
-            case 32: PAI_SATTN_BF16(32); break;
-            case 64: PAI_SATTN_BF16(64); break;
-            case 128: PAI_SATTN_BF16(128); break;
+    hipLaunchKernelGGL((sattn_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, T, heads, scale2, (bf16_t*)out, lse)
+        switch (sel.idx) {
+            case 0: PAI_SATTN_BF16(32); break;
+            case 1: PAI_SATTN_BF16(64); break;
+            case 2: PAI_SATTN_BF16(128); break;
             default: PAI_SATTN_BF16(256); break;
         }
 #undef PAI_SATTN_BF16
     } else {
         const dim3 grid(cdiv(T, 32), N * heads);
 #define PAI_SATTN_F32(CH, KVB) \
-    hipLaunchKernelGGL((sattn_f32_k<CH, KVB>), grid, dim3(256), 0, s, (const float*)qkv, T, heads, scale2, (float*)out)
-        switch (ch) {
-            case 32: PAI_SATTN_F32(32, 32); break;
-            case 64: PAI_SATTN_F32(64, 32); break;
-            case 128: PAI_SATTN_F32(128, 32); break;
+    hipLaunchKernelGGL((sattn_f32_k<CH, KVB>), grid, dim3(256), 0, s, (const float*)qkv, T, heads, scale2, (float*)out, lse)
+        switch (sel.idx) {
+            case 0: PAI_SATTN_F32(32, 32); break;
+            case 1: PAI_SATTN_F32(64, 32); break;
+            case 2: PAI_SATTN_F32(128, 32); break;
             default: PAI_SATTN_F32(256, 16); break;
         }
 #undef PAI_SATTN_F32
     }
     PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pai_sattn_fwd(int dtype, const void* qkv, int N, int T, int heads, int ch, void* out, void* stream) {
+    return sattn_forward("pai_sattn_fwd", dtype, qkv, N, T, heads, ch, out, nullptr, stream);
+}
+
+extern "C" int pai_sattn_fwd_lse(int dtype, const void* qkv, int N, int T, int heads, int ch, void* out, float* lse,
+                                 void* stream) {
+    PAI_CHECK(lse, "pai_sattn_fwd_lse: null tensor");
+    return sattn_forward("pai_sattn_fwd_lse", dtype, qkv, N, T, heads, ch, out, lse, stream);
+}
+
+extern "C" int pai_sattn_bwd(int dtype, const void* dout, const void* qkv, const void* out, const float* lse, int N, int T,
+                             int heads, int ch, void* dqkv, float* ws, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_sattn_bwd: dtype=%d", dtype);
+    PAI_CHECK(dout && qkv && out && lse && dqkv && ws, "pai_sattn_bwd: null tensor");
+    if (sattn_check("pai_sattn_bwd", dtype, N, T, heads, ch)) return 1;
+    const SattnSel sel = sattn_select(dtype, ch);
+    PAI_CHECK(sel.bwd_ok, "pai_sattn_bwd: ch=256 has no bf16 backward (bf16: 32, 64 or 128 channels per head; fp32 also 256)");
+    PAI_CHECK((((uintptr_t)dout) | ((uintptr_t)qkv) | ((uintptr_t)out) | ((uintptr_t)lse) | ((uintptr_t)dqkv) | ((uintptr_t)ws)) % 16 == 0,
+              "pai_sattn_bwd: tensors must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const float scale2 = 1.0f / sqrtf((float)ch);
+    const int64_t rows = (int64_t)N * T * heads;
+    PAI_CHECK(rows * (ch / 8) < ((int64_t)1 << 31) * 256, "pai_sattn_bwd: too many rows");
+    const dim3 dgrid(cdiv(rows * (ch / 8), 256));
+    if (dtype == PAI_BF16) {
+        const dim3 grid(cdiv(T, 128), N * heads);
+#define PAI_SATTN_BWD_BF16(CH)                                                                                                 \
+    hipLaunchKernelGGL((sattn_bwd_delta_k<bf16_t, CH>), dgrid, dim3(256), 0, s, (const bf16_t*)dout, (const bf16_t*)out, rows, \
+                       T, heads, ws);                                                                                          \
+    hipLaunchKernelGGL((sattn_bwd_kv_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse,         \
+                       (const float*)ws, T, heads, scale2, (bf16_t*)dqkv);                                                     \
+    hipLaunchKernelGGL((sattn_bwd_q_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse,          \
+                       (const float*)ws, T, heads, scale2, (bf16_t*)dqkv)
+        switch (sel.idx) {
+            case 0: PAI_SATTN_BWD_BF16(32); break;
+            case 1: PAI_SATTN_BWD_BF16(64); break;
+            default: PAI_SATTN_BWD_BF16(128); break;
+        }
+#undef PAI_SATTN_BWD_BF16
+    } else {
+        const dim3 grid(cdiv(T, 32), N * heads);
+#define PAI_SATTN_BWD_F32(CH, OB)                                                                                           \
+    hipLaunchKernelGGL((sattn_bwd_delta_k<float, CH>), dgrid, dim3(256), 0, s, (const float*)dout, (const float*)out, rows, \
+                       T, heads, ws);                                                                                       \
+    hipLaunchKernelGGL((sattn_bwd_f32_k<CH, OB, true>), grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse,  \
+                       (const float*)ws, T, heads, scale2, (float*)dqkv);                                                   \
+    hipLaunchKernelGGL((sattn_bwd_f32_k<CH, OB, false>), grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, \
+                       (const float*)ws, T, heads, scale2, (float*)dqkv)
+        switch (sel.idx) {
+            case 0: PAI_SATTN_BWD_F32(32, 32); break;
+            case 1: PAI_SATTN_BWD_F32(64, 32); break;
+            case 2: PAI_SATTN_BWD_F32(128, 32); break;
+            default: PAI_SATTN_BWD_F32(256, 16); break;
+        }
+#undef PAI_SATTN_BWD_F32
+    }
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pai_sattn_kernel_name(int dtype, int ch, int op, char* name, int name_len) {
+    PAI_CHECK(name && name_len > 0, "pai_sattn_kernel_name: bad arguments");
+    PAI_CHECK(op == 0 || op == 1, "pai_sattn_kernel_name: op %d (0 forward, 1 backward)", op);
+    if (sattn_check("pai_sattn_kernel_name", dtype, 1, 1, 1, ch)) return 1;
+    const SattnSel sel = sattn_select(dtype, ch);
+    PAI_CHECK(op == 0 || sel.bwd_ok,
+              "pai_sattn_kernel_name: ch=256 has no bf16 backward (bf16: 32, 64 or 128 channels per head; fp32 also 256)");
+    snprintf(name, (size_t)name_len, "%s", op == 0 ? sel.fwd : sel.bwd);
     return 0;
 }
 

@@ -520,3 +520,53 @@ def eval_images(pred, target, denorm=False, strips=0, ssim_map=False, hot=False)
                       sse=sse,
                       strip_ssim=strip_pl.view(n, c, strips).mean(dim=1).float() if strips else None,
                       ssim_map_u8=map_u8, hot_u8=hot_u8)
+
+
+# --------------------------------------------------------------------------------------
+# spatial attention of the Palette levels (differentiable)
+# --------------------------------------------------------------------------------------
+class _SpatialAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, heads, ch):
+        n, t = qkv.shape[0], qkv[0].numel() // qkv.shape[-1]
+        out = torch.empty(qkv.shape[:-1] + (heads * ch,), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty((n, heads, t), dtype=torch.float32, device=qkv.device)
+        ops.sattn_fwd_lse(qkv.dtype, qkv, n, t, heads, ch, out, lse)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.dims = (n, t, heads, ch)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        qkv, out, lse = ctx.saved_tensors
+        n, t, heads, ch = ctx.dims
+        if g.dtype != qkv.dtype:
+            raise ops.PaiError(f"spatial_attention: gradient of {g.dtype} for an output of {qkv.dtype}")
+        dqkv = torch.empty_like(qkv)
+        ws = torch.empty(n * heads * t, dtype=torch.float32, device=qkv.device)
+        ops.sattn_bwd(qkv.dtype, g.contiguous(), qkv, out, lse, n, t, heads, ch, dqkv, ws)
+        return dqkv, None, None
+
+
+def spatial_attention(qkv, heads: int):
+    """QKVAttentionLegacy (reference models/guided_diffusion/unet.py:265-297) with a backward: qkv [N, T, 3 C] or NHWC
+    [N, H, W, 3 C] (fp32 or bf16, contiguous, on the device; the channel order [head][q | k | v][ch] of the 1 x 1 qkv
+    convolution) -> [..., C].  Neither direction stores the T x T scores: the forward keeps qkv, out and the fp32 log-sum-exp of
+    every query, the backward recomputes the probabilities from them (``pai_sattn_bwd``).  No host synchronisation."""
+    if not isinstance(qkv, torch.Tensor) or not qkv.is_cuda:
+        raise ops.PaiError("spatial_attention needs a HIP device tensor (no CPU fallback exists)")
+    if qkv.dim() not in (3, 4) or qkv.numel() == 0:
+        raise ops.PaiError(f"spatial_attention: qkv of shape {tuple(qkv.shape)} ([N, T, 3 C] or [N, H, W, 3 C])")
+    if not qkv.is_contiguous():
+        raise ops.PaiError("spatial_attention: qkv must be contiguous")
+    width = qkv.shape[-1]
+    if heads < 1 or width % (3 * heads):
+        raise ops.PaiError(f"spatial_attention: width {width} is not divisible by 3 * heads = {3 * heads}")
+    ch = width // (3 * heads)
+    bwd_ok = (32, 64, 128, 256) if qkv.dtype == torch.float32 else (32, 64, 128)
+    ops.code_of(qkv.dtype)
+    if ch not in bwd_ok:
+        raise ops.PaiError(f"spatial_attention: ch={ch} per head is not supported in {qkv.dtype} (fp32: 32, 64, 128 or 256; "
+                           f"bf16: 32, 64 or 128)")
+    return _SpatialAttention.apply(qkv, int(heads), ch)

@@ -185,6 +185,9 @@ SIGNATURES = {
     "pai_batch_gather": (_I, [_I, _P, _P, _L, _L, _P, _I, _P, _P, _P, _P]),
     "pai_data_kernel_name": (_I, [_I, _I, C.c_char_p, _I]),
     "pai_sattn_fwd": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
+    "pai_sattn_fwd_lse": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "pai_sattn_bwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "pai_sattn_kernel_name": (_I, [_I, _I, _I, C.c_char_p, _I]),
     "pai_affine_act": (_I, [_I, _P, _L, _I, _I, _P, _P, _I, _I, _P, _P]),
     "pai_film_coeffs": (_I, [_I, _I, _I, _P, _P, _P, _L, _P, _P, _P]),
     "pai_avgpool2": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),

@@ -1119,6 +1119,30 @@ def sattn_fwd(dtype, qkv, N, T, heads, ch, out):
                                    _stream()), "pai_sattn_fwd")
 
 
+def sattn_fwd_lse(dtype, qkv, N, T, heads, ch, out, lse):
+    """``sattn_fwd`` (the same kernels, the same out bits) that also writes lse fp32 [N][heads][T], the natural-log sum-exp
+    of every query's scaled scores (pai_sattn_fwd_lse)."""
+    L.check(L.load().pai_sattn_fwd_lse(code_of(dtype), _p(qkv, dtype), int(N), int(T), int(heads), int(ch), _p(out, dtype),
+                                       _p(lse, torch.float32), _stream()), "pai_sattn_fwd_lse")
+
+
+def sattn_bwd(dtype, dout, qkv, out, lse, N, T, heads, ch, dqkv, ws):
+    """dqkv (qkv's layout) from dout, qkv and the forward's out / lse without the T x T scores; ws fp32 [N * heads * T]
+    receives delta (pai_sattn_bwd)."""
+    L.check(L.load().pai_sattn_bwd(code_of(dtype), _p(dout, dtype), _p(qkv, dtype), _p(out, dtype), _p(lse, torch.float32),
+                                   int(N), int(T), int(heads), int(ch), _p(dqkv, dtype), _p(ws, torch.float32), _stream()),
+            "pai_sattn_bwd")
+
+
+def sattn_kernel_name(dtype, ch, op: int = 0) -> str:
+    """rocprofv3 symbol(s) of the kernels behind ``sattn_fwd`` / ``sattn_fwd_lse`` (op 0) and ``sattn_bwd`` (op 1, three
+    launches joined by '+') at this dtype and head width: the selection the launchers branch on (host only)."""
+    buf = C.create_string_buffer(160)
+    if L.load().pai_sattn_kernel_name(code_of(dtype), int(ch), int(op), buf, 160) != 0:
+        L.check(1, "pai_sattn_kernel_name")
+    return buf.value.decode()
+
+
 def affine_act(dtype, x, rows_per_sample, N, C_, A, B, per_sample, act, out):
     """out = act(x * A + B) on [N][rows][C]; A, B fp32 [C] or (per_sample) [N][C]; act none | SiLU (pai_affine_act)."""
     if A.numel() != (N * C_ if per_sample else C_) or B.numel() != A.numel():
