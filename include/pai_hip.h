@@ -43,7 +43,7 @@ extern "C" {
 #define PAI_ACT_LRELU 1   /* LeakyReLU(0.2)  models/pix2pix.py:62, models/wrapper.py:205 */
 #define PAI_ACT_RELU 2    /* ReLU            models/pix2pix.py:98 */
 #define PAI_ACT_TANH 3    /* Tanh            models/pix2pix.py:196 */
-#define PAI_ACT_SILU 4    /* v * sigmoid(v)  models/guided_diffusion/unet.py:18-20; pai_affine_act only */
+#define PAI_ACT_SILU 4    /* v * sigmoid(v)  models/guided_diffusion/unet.py:18-20; pai_affine_act and pai_film_norm_* only */
 
 const char* pai_last_error(void);
 /* 100: round 1.  110: per-device handles, pai_set_tunable, pai_adam_dev, pai_scalar_take / pai_metrics_take,
@@ -64,7 +64,9 @@ const char* pai_last_error(void);
  * 136: pai_mha_kernel_name.
  * 137: pai_denormalize and the fused `denorm` of the metric entry points keep a NaN (torch.clamp); they returned 0 for it;
  * the multi-tensor calls (pai_adam_multi, pai_adam_multi_dev, pai_zero_multi, pai_lerp_multi) accept NULL for a tensor of 0 elements.
- * 138: differentiable spatial attention (pai_sattn_fwd_lse, pai_sattn_bwd, pai_sattn_kernel_name). */
+ * 138: differentiable spatial attention (pai_sattn_fwd_lse, pai_sattn_bwd, pai_sattn_kernel_name).
+ * 139: train-mode FiLM norm (pai_film_norm_fwd, pai_film_norm_bwd, pai_film_norm_ws_floats, pai_film_norm_slabs); PAI_ACT_SILU
+ * is also taken by these. */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -788,6 +790,41 @@ int pai_gamma_embedding(int dtype, const float* gammas, int N, int dim, void* ou
 int pai_palette_step(int dtype, const void* model_out, const float* y_t, const float* noise, int64_t pixels, int C,
                      int learn_var, int add_noise, float s1, float rs, float c0, float c1, float log_lo, float log_hi,
                      float* y_next, void* xy_next, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Train-mode norm sites of the guided-diffusion U-Net (ABI 139; reference models/guided_diffusion/unet.py:141-172,206-210,
+ * nn.py:16-23,51-68): BatchNorm on batch statistics, the per-sample FiLM scale / shift, SiLU and element-wise Dropout as one
+ * differentiable op.  Per channel c, sample n and position p of x [N][rows][C] (NHWC), M = N * rows:
+ *     xhat = (x - mean_c) rstd_c,  v = gamma_c xhat + beta_c,  u = v (1 + s_nc) + t_nc,  y = m_npc k act(u)
+ *     du = g m k act'(u),  S0_nc = sum_p du,  S1_nc = sum_p du xhat,  dt_nc = S0_nc,  ds_nc = gamma_c S1_nc + beta_c S0_nc,
+ *     dbeta_c = sum_n (1 + s_nc) S0_nc,  dgamma_c = sum_n (1 + s_nc) S1_nc,
+ *     dx = gamma_c rstd_c (du (1 + s_nc) - dbeta_c / M - xhat dgamma_c / M)
+ * dtype PAI_F32 | PAI_BF16 is the storage type of x, out, g, dx, emb and demb; mean, rstd (the batch statistics of
+ * pai_bn_stats + pai_bn_finalize, biased variance), gamma, beta, dgamma, dbeta and ws are fp32, and all arithmetic and all sums
+ * are fp32 (the sum over slabs and samples: fp64).  C is a multiple of 8, 8 <= C <= 2048; N <= 65535.  emb: [N] rows of ld
+ * elements (ld >= 2 C), s = columns [0, C), t = columns [C, 2 C) (the layout of pai_film_coeffs); NULL: s = t = 0.  mask: uint8
+ * [N][rows][C], 0 drops the element, any other value keeps it; NULL: m = 1 (keep_scale is then not read).  keep_scale = k =
+ * 1 / (1 - p).  act: PAI_ACT_NONE | PAI_ACT_SILU; SiLU'(u) = sig(u) (1 + u (1 - sig(u))), sig and 1 - sig formed from exp(-|u|):
+ * finite at u = +-100, a NaN stays a NaN.  fp32 uses expf and a division, bf16 the hardware exp2 and reciprocal.  Tensors are
+ * 16-byte aligned, the mask 8-byte.  Everything else is refused before any launch.
+ * pai_film_norm_fwd: y in one pass, xhat formed first, then one fma with the per-thread coefficients gamma (1 + s) and
+ * beta (1 + s) + t.  out may alias x.
+ * pai_film_norm_bwd: three launches.  reduce, grid (slabs, N): the workgroup of a (slab, sample) rebuilds du from g, x and mask
+ * and writes its partial S0, S1 to ws (a slab that owns no row writes zeros); finalize: the slabs, then the samples, summed in
+ * fp64 in a fixed order; demb (dtype, emb's layout: ds in columns [0, C), dt in [C, 2 C), the other columns untouched; not
+ * written when emb is NULL), dgamma[c] += and dbeta[c] += (either may be NULL), and dbeta / M, dgamma / M behind the partial
+ * sums in ws; apply: du rebuilt again, dx written.  du is never stored; dx may alias g.  No atomics, no sum across workgroups
+ * in arrival order: the same bits on every run.  ws: pai_film_norm_ws_floats(N, rows, C) floats, caller-provided, any content.
+ * pai_film_norm_slabs(rows): the slabs the rows of a sample are split into, min(256, ceil(rows / 64)); slab i owns the rows
+ * [i rps, (i + 1) rps) below `rows`, rps = ceil(rows / slabs) -- the last slabs may own none. */
+int pai_film_norm_slabs(int64_t rows);
+int64_t pai_film_norm_ws_floats(int N, int64_t rows, int C);
+int pai_film_norm_fwd(int dtype, const void* x, int64_t rows, int N, int C, const float* mean, const float* rstd,
+                      const float* gamma, const float* beta, const void* emb, int64_t ld, const unsigned char* mask,
+                      float keep_scale, int act, void* out, void* stream);
+int pai_film_norm_bwd(int dtype, const void* g, const void* x, int64_t rows, int N, int C, const float* mean, const float* rstd,
+                      const float* gamma, const float* beta, const void* emb, int64_t ld, const unsigned char* mask,
+                      float keep_scale, int act, void* dx, void* demb, float* dgamma, float* dbeta, float* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,12 +2,17 @@
 beside ``torch.nn.functional.scaled_dot_product_attention`` on the same data (both as TFLOP/s of 4 N heads T^2 ch), then
 ``pai_sattn_bwd`` (its three launches) beside the backward of the same SDPA call (both as TFLOP/s of the algorithmic
 10 N heads T^2 ch; the kernels recompute S and execute 14).
+Last the train-mode norm site ``pai_film_norm_fwd`` / ``pai_film_norm_bwd`` (FiLM + SiLU + mask, bf16) at the class-default levels,
+as GB/s of the bytes the passes must move (forward: 2 tensors + the mask; backward: 5 tensors + 2 masks), beside torch's own
+``batch_norm`` + FiLM + ``silu`` + mask forward and autograd on the same shapes (NCHW, torch's layout) and charged the same bytes.
 Random normal data throughout (never zeros: MI355X_MICROARCH, data-dependent power).  One JSON line per measurement.
 
     python scripts/bench_palette.py [--precision bf16-mixed] [--batch 8] [--size 256] [--steps 100] [--mults 1,1,2,2,4,4]
                                     [--attention-res 16,8] [--no-sampler] [--no-attention] [--forward-only K]
+                                    [--no-film-norm] [--film-norm-only]
 
-``--forward-only K`` runs K U-Net forward passes and nothing else (the run to put under a kernel trace).
+``--forward-only K`` runs K U-Net forward passes and nothing else (the run to put under a kernel trace); ``--film-norm-only``
+runs the film_norm rows and nothing else (no model is built).
 """
 import argparse
 import json
@@ -83,6 +88,50 @@ def bench_attention_bwd(dtype, n, heads, T, ch, qkv, iters):
     print(json.dumps(row), flush=True)
 
 
+FILM_NORM_SHAPES = [(65536, 64), (16384, 128), (1024, 256), (256, 256)]      # (rows, C) per sample: the class defaults at 256 x 256
+
+
+def bench_film_norm(dtype, n):
+    es = torch.empty(0, dtype=dtype).element_size()
+    for rows, C in FILM_NORM_SHAPES:
+        numel = n * rows * C
+        x, g = (torch.randn(n, rows, C, device="cuda").to(dtype) for _ in range(2))
+        emb = (0.3 * torch.randn(n, 2 * C, device="cuda")).to(dtype)
+        gamma, beta = 1 + 0.1 * torch.randn(C, device="cuda"), 0.1 * torch.randn(C, device="cuda")
+        mask = (torch.rand(n, rows, C, device="cuda") >= 0.1).to(torch.uint8)
+        keep = 1.0 / 0.9
+        mean, rstd = x.float().mean((0, 1)), 1.0 / torch.sqrt(x.float().var((0, 1), unbiased=False) + 1e-5)
+        out, dx, demb = torch.empty_like(x), torch.empty_like(x), torch.empty_like(emb)
+        dgb = torch.zeros(2 * C, device="cuda")
+        ws = torch.empty(ops.film_norm_ws_floats(n, rows, C), device="cuda")
+        iters = 20 if numel > (1 << 24) else 100
+        fwd_bytes, bwd_bytes = numel * (2 * es + 1), numel * (5 * es + 2)
+        fms = timed(lambda: ops.film_norm_fwd(dtype, x, rows, n, C, mean, rstd, gamma, beta, emb, 2 * C, mask, keep, ops.ACT_SILU,
+                                              out), 3, iters)
+        bms = timed(lambda: ops.film_norm_bwd(dtype, g, x, rows, n, C, mean, rstd, gamma, beta, emb, 2 * C, mask, keep,
+                                              ops.ACT_SILU, dx, demb, dgb[:C], dgb[C:], ws), 3, iters)
+        row = {"bench": "film_norm", "dtype": str(dtype), "N": n, "rows": rows, "C": C, "fwd_ms": round(fms, 4),
+               "fwd_GBps": round(fwd_bytes / fms / 1e6, 1), "bwd_ms": round(bms, 4), "bwd_GBps": round(bwd_bytes / bms / 1e6, 1)}
+        # torch: the same site in its own layout, statistics included (it has no entry without them)
+        side = int(rows ** 0.5)
+        xt = x.view(n, side, side, C).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+        gt = g.view(n, side, side, C).permute(0, 3, 1, 2).contiguous()
+        mt = mask.view(n, side, side, C).permute(0, 3, 1, 2).contiguous().to(dtype) * keep
+        et = emb.detach().requires_grad_(True)
+        gw, bw = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+
+        def torch_fwd():
+            v = torch.nn.functional.batch_norm(xt.float(), None, None, gw, bw, True, 0.1, 1e-5).to(dtype)
+            return torch.nn.functional.silu(v * (1 + et[:, :C, None, None]) + et[:, C:, None, None]) * mt
+
+        tf = timed(torch_fwd, 3, iters)
+        yt = torch_fwd()
+        tb = timed(lambda: torch.autograd.grad(yt, (xt, et, gw, bw), gt, retain_graph=True), 3, iters)
+        row.update(torch_fwd_ms=round(tf, 4), torch_fwd_GBps=round(fwd_bytes / tf / 1e6, 1), torch_bwd_ms=round(tb, 4),
+                   torch_bwd_GBps=round(bwd_bytes / tb / 1e6, 1))
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="bf16-mixed")
@@ -94,7 +143,13 @@ def main():
     ap.add_argument("--no-sampler", action="store_true")
     ap.add_argument("--no-attention", action="store_true")
     ap.add_argument("--forward-only", type=int, default=0)
+    ap.add_argument("--no-film-norm", action="store_true")
+    ap.add_argument("--film-norm-only", action="store_true")
     a = ap.parse_args()
+    if a.film_norm_only:
+        torch.manual_seed(0)
+        bench_film_norm(torch.bfloat16, a.batch)
+        return
     torch.manual_seed(0)
     dev = torch.device("cuda:0")
     mults, att = tuple(int(v) for v in a.mults.split(",")), tuple(int(v) for v in a.attention_res.split(","))
@@ -126,6 +181,8 @@ def main():
                           "ms_per_unet_forward": round(ms / a.steps, 3)}), flush=True)
     if not a.no_attention:
         bench_attention(dtype, a.batch, 4)
+    if not a.no_film_norm:
+        bench_film_norm(torch.bfloat16, a.batch)
 
 
 if __name__ == "__main__":

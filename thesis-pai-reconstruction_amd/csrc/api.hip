@@ -14,7 +14,7 @@ void pai_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* pai_last_error(void) { return g_err; }
-extern "C" int pai_version(void) { return 138; }   // 110: handles, tunables, device-side Adam step, *_take, pack multi; 120: weight-gradient workspace; 121: pai_adam_pack, pai_bn_bwd_apply_affine; 130: launch plans; 131: pai_lerp_multi; 132: input prologue (pai_conv_fwd_pro / pai_conv_wgrad_pro); 133: device-resident data set (data.hip); 134: report evaluation (eval.hip); 135: Palette sampling (palette.hip); 136: pai_mha_kernel_name; 137: denormalize keeps NaN, empty tensors in the multi-tensor calls
+extern "C" int pai_version(void) { return 139; }   // 110: handles, tunables, device-side Adam step, *_take, pack multi; 120: weight-gradient workspace; 121: pai_adam_pack, pai_bn_bwd_apply_affine; 130: launch plans; 131: pai_lerp_multi; 132: input prologue (pai_conv_fwd_pro / pai_conv_wgrad_pro); 133: device-resident data set (data.hip); 134: report evaluation (eval.hip); 135: Palette sampling (palette.hip); 136: pai_mha_kernel_name; 137: denormalize keeps NaN, empty tensors in the multi-tensor calls; 138: differentiable spatial attention; 139: train-mode FiLM norm (film_norm.hip)
 
 // build-option bits; none since ABI 130 (bit 0 announced the round-2 experiment kernels, which were removed)
 extern "C" int pai_build_flags(void) { return 0; }

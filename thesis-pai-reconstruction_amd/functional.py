@@ -570,3 +570,89 @@ def spatial_attention(qkv, heads: int):
         raise ops.PaiError(f"spatial_attention: ch={ch} per head is not supported in {qkv.dtype} (fp32: 32, 64, 128 or 256; "
                            f"bf16: 32, 64 or 128)")
     return _SpatialAttention.apply(qkv, int(heads), ch)
+
+
+# --------------------------------------------------------------------------------------
+# train-mode BatchNorm + FiLM + SiLU + Dropout of the Palette blocks (differentiable)
+# --------------------------------------------------------------------------------------
+class _FilmNormAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, emb_out, mask, keep_scale, act, running_mean, running_var, nbt, momentum, eps):
+        n, c = x.shape[0], x.shape[-1]
+        rows = x[0].numel() // c
+        m, dtype = n * rows, x.dtype
+        f32 = dict(dtype=torch.float32, device=x.device)
+        srows = ops.bn_stats_rows(m)
+        stats = torch.empty(ops.bn_stats_buffer_rows(srows) * 2 * c, **f32)
+        ops.bn_stats(dtype, x, m, c, stats)
+        mean, rstd, scale, shift = (torch.empty(c, **f32) for _ in range(4))
+        # detached aliases (as ConvBNAct saves them): autograd's version check does not see an in-place update of weight / bias
+        # between forward and backward -- step the optimizer after the backward.  The running buffers are advanced in place
+        # here, as nn.BatchNorm advances them in its forward; they are no inputs of the graph, hence no mark_dirty.
+        gamma, beta = weight.detach(), bias.detach()
+        ops.bn_finalize(stats, srows, c, m, gamma, beta, eps, momentum, 1, running_mean, running_var, nbt, mean, rstd, scale,
+                        shift)
+        ld = emb_out.shape[1] if emb_out is not None else 0
+        out = torch.empty_like(x)
+        ops.film_norm_fwd(dtype, x, rows, n, c, mean, rstd, gamma, beta, emb_out, ld, mask, keep_scale, act, out)
+        ctx.save_for_backward(x, mean, rstd, gamma, beta, emb_out, mask)
+        ctx.dims = (n, rows, c, ld, keep_scale, act)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, mean, rstd, gamma, beta, emb_out, mask = ctx.saved_tensors
+        n, rows, c, ld, keep_scale, act = ctx.dims
+        if g.dtype != x.dtype:
+            raise ops.PaiError(f"film_norm_act: gradient of {g.dtype} for an output of {x.dtype}")
+        f32 = dict(dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        # the columns of demb past 2 C belong to nobody: zero, as the gradient of columns the op does not read
+        demb = torch.zeros_like(emb_out) if emb_out is not None else None
+        dgb = torch.zeros(2 * c, **f32)
+        ws = torch.empty(ops.film_norm_ws_floats(n, rows, c), **f32)
+        ops.film_norm_bwd(x.dtype, g.contiguous(), x, rows, n, c, mean, rstd, gamma, beta, emb_out, ld, mask, keep_scale, act, dx,
+                          demb, dgb[:c], dgb[c:], ws)
+        return (dx, dgb[:c], dgb[c:], demb) + (None,) * 8
+
+
+def film_norm_act(x, weight, bias, emb_out=None, *, act="silu", dropout_mask=None, p=0.0, running_mean=None, running_var=None,
+                  num_batches_tracked=None, momentum=0.1, eps=1e-5):
+    """A norm site of the guided-diffusion U-Net in training (reference models/guided_diffusion/unet.py:141-172,206-210):
+    ``Dropout(act(BatchNorm(x) * (1 + scale) + shift))`` on batch statistics, with a backward.  x: [N, rows, C] or NHWC
+    [N, H, W, C] (fp32 or bf16, contiguous, on the device); weight, bias: fp32 [C]; emb_out: None or [N, >= 2 C] of x's dtype with
+    ``scale | shift`` in its first 2 C columns, contiguous (the output of ``emb_layers``); act: "silu" or "none";
+    dropout_mask: uint8 of x's shape, 0 drops; with p > 0 and no mask one is drawn with ``torch.rand`` on the current stream.
+    running_mean / running_var / num_batches_tracked are updated in place as nn.BatchNorm does when they are given.  The
+    forward keeps x, mean, rstd, emb_out and the mask, not its output; the backward returns the gradients of x, weight, bias
+    and emb_out (``pai_film_norm_fwd`` / ``pai_film_norm_bwd``).  No host synchronisation."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ops.PaiError("film_norm_act needs a HIP device tensor (no CPU fallback exists)")
+    if x.dim() not in (3, 4) or x.numel() == 0:
+        raise ops.PaiError(f"film_norm_act: x of shape {tuple(x.shape)} ([N, rows, C] or [N, H, W, C])")
+    if not x.is_contiguous():
+        raise ops.PaiError("film_norm_act: x must be contiguous")
+    ops.code_of(x.dtype)
+    n, c = x.shape[0], x.shape[-1]
+    if act not in ("silu", "none"):
+        raise ops.PaiError(f"film_norm_act: act={act!r} ('silu' or 'none')")
+    if c % 8 or not 8 <= c <= 2048:
+        raise ops.PaiError(f"film_norm_act: C={c} (a multiple of 8, at most 2048)")
+    for name, t in (("weight", weight), ("bias", bias)):
+        if t.dtype != torch.float32 or t.shape != (c,) or not t.is_contiguous():
+            raise ops.PaiError(f"film_norm_act: {name} must be a contiguous fp32 [C] tensor")
+    if emb_out is not None:
+        if emb_out.dim() != 2 or emb_out.shape[0] != n or emb_out.shape[1] < 2 * c or not emb_out.is_contiguous() \
+                or emb_out.dtype != x.dtype:
+            raise ops.PaiError(f"film_norm_act: emb_out must be a contiguous [N, >= 2 C] tensor of {x.dtype}")
+    if not 0.0 <= p < 1.0:
+        raise ops.PaiError(f"film_norm_act: p={p}")
+    if dropout_mask is None and p > 0.0:
+        dropout_mask = (torch.rand(x.shape, device=x.device) >= p).to(torch.uint8)
+    if dropout_mask is not None and (dropout_mask.dtype != torch.uint8 or dropout_mask.shape != x.shape
+                                     or not dropout_mask.is_contiguous()):
+        raise ops.PaiError("film_norm_act: dropout_mask must be a contiguous uint8 tensor of x's shape")
+    keep_scale = 1.0 / (1.0 - p) if dropout_mask is not None else 1.0
+    return _FilmNormAct.apply(x, weight, bias, emb_out, dropout_mask, keep_scale, ops.ACT_SILU if act == "silu" else ops.ACT_NONE,
+                              running_mean, running_var, num_batches_tracked, float(momentum), float(eps))

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("PAI_HIP_LIB") or os.path.join(HERE, "libpai_hip.so")
 F32, BF16 = 0, 1
 U8 = 2          # PAI_U8: image bytes of the device-resident data set
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
-ACT_SILU = 4       # PAI_ACT_SILU: pai_affine_act only
+ACT_SILU = 4       # PAI_ACT_SILU: pai_affine_act and pai_film_norm_* only
 HINT_SOLO = 1
 
 
@@ -193,6 +193,10 @@ SIGNATURES = {
     "pai_avgpool2": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
     "pai_gamma_embedding": (_I, [_I, _P, _I, _I, _P, _P]),
     "pai_palette_step": (_I, [_I, _P, _P, _P, _L, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
+    "pai_film_norm_slabs": (_I, [_L]),
+    "pai_film_norm_ws_floats": (_L, [_I, _L, _I]),
+    "pai_film_norm_fwd": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _F, _I, _P, _P]),
+    "pai_film_norm_bwd": (_I, [_I, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _F, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1177,3 +1177,34 @@ def palette_step(dtype, model_out, y_t, noise, pixels, C_, learn_var, add_noise,
     L.check(L.load().pai_palette_step(code_of(dtype), _p(model_out, dtype), _p(y_t, torch.float32), _p(noise, torch.float32),
                                       int(pixels), int(C_), int(bool(learn_var)), int(bool(add_noise)), s1, rs, c0, c1, llo,
                                       lhi, _p(y_next, torch.float32), _p(xy_next, dtype), _stream()), "pai_palette_step")
+
+
+# ---- train-mode norm sites of the guided-diffusion U-Net (csrc/film_norm.hip) -----------------------------------------
+def film_norm_slabs(rows) -> int:
+    """Slabs the rows of one sample are split into by ``film_norm_fwd`` / ``film_norm_bwd`` (pai_film_norm_slabs)."""
+    return L.load().pai_film_norm_slabs(int(rows))
+
+
+def film_norm_ws_floats(N, rows, C_) -> int:
+    """fp32 elements of the workspace of ``film_norm_bwd`` (pai_film_norm_ws_floats)."""
+    return L.load().pai_film_norm_ws_floats(int(N), int(rows), int(C_))
+
+
+def film_norm_fwd(dtype, x, rows, N, C_, mean, rstd, gamma, beta, emb, ld, mask, keep_scale, act, out):
+    """out = m k act((gamma xhat + beta)(1 + s) + t) on [N][rows][C] from the batch statistics mean / rstd; emb (dtype, rows of
+    ``ld`` elements, s | t in columns [0, C) | [C, 2 C)) and mask (uint8) may be None (pai_film_norm_fwd)."""
+    L.check(L.load().pai_film_norm_fwd(code_of(dtype), _p(x, dtype), int(rows), int(N), int(C_), _p(mean, torch.float32),
+                                       _p(rstd, torch.float32), _p(gamma, torch.float32), _p(beta, torch.float32),
+                                       _p(emb, dtype), int(ld), _p(mask, torch.uint8), float(keep_scale), int(act),
+                                       _p(out, dtype), _stream()), "pai_film_norm_fwd")
+
+
+def film_norm_bwd(dtype, g, x, rows, N, C_, mean, rstd, gamma, beta, emb, ld, mask, keep_scale, act, dx, demb, dgamma, dbeta,
+                  ws):
+    """dx, demb (emb's layout: ds | dt), dgamma +=, dbeta += from g = dL/dy and the forward's inputs in three launches; ws fp32
+    [film_norm_ws_floats(N, rows, C)] (pai_film_norm_bwd)."""
+    L.check(L.load().pai_film_norm_bwd(code_of(dtype), _p(g, dtype), _p(x, dtype), int(rows), int(N), int(C_),
+                                       _p(mean, torch.float32), _p(rstd, torch.float32), _p(gamma, torch.float32),
+                                       _p(beta, torch.float32), _p(emb, dtype), int(ld), _p(mask, torch.uint8),
+                                       float(keep_scale), int(act), _p(dx, dtype), _p(demb, dtype), _p(dgamma, torch.float32),
+                                       _p(dbeta, torch.float32), _p(ws, torch.float32), _stream()), "pai_film_norm_bwd")
