@@ -1,8 +1,9 @@
-"""Re-check the launch-configuration defaults of the tile kernels on the bench: one bench.py run per environment."""
+"""Re-check the launch-configuration defaults of the convolution kernels on the bench: one bench.py run per setting of a
+tunable (its PAI_TUNE_<name> default)."""
 import json, os, subprocess, sys
-SWEEP = [{}, {"PAI_FWD_MODE": "1"}, {"PAI_FWD_MODE": "2"}, {"PAI_PATCH_DBB": "7"}, {"PAI_PATCH_DBB": "1"}, {"PAI_PATCH_DBB": "2"},
-         {"PAI_PATCH_DBB": "0"}, {"PAI_WGRAD_TARGET": "512"}, {"PAI_WGRAD_TARGET": "1024"}, {"PAI_WGRAD_TARGET": "1536"},
-         {"PAI_NO_WPATCH": "1"}, {"PAI_WGRAD_MINROWS": "1024"}, {"PAI_TW_BLOCKS": "2048"}, {}]
+SWEEP = [{}, {"PAI_TUNE_fwd_patch256": "0"}, {"PAI_TUNE_wgrad_target": "512"}, {"PAI_TUNE_wgrad_target": "1024"},
+         {"PAI_TUNE_wgrad_target": "1536"}, {"PAI_TUNE_wgrad_patch": "0"}, {"PAI_TUNE_wgrad_minrows": "1024"},
+         {"PAI_TUNE_thin_wgrad_blocks": "2048"}, {}]
 for env in SWEEP:
     r = subprocess.run([sys.executable, "bench.py", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-kernel-events"],
                        env=dict(os.environ, **env), capture_output=True, text=True)

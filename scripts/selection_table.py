@@ -4,7 +4,7 @@ rows, workspace / scratch / weight-gradient workspace bytes, partial-row bound, 
     python scripts/selection_table.py OUT.json               no GPU needed (un-split names, no slab-dependent answers)
     python scripts/selection_table.py OUT.json --register    GPU box: workspace, scratch and weight-gradient slab registered
     python scripts/selection_table.py --diff A.json B.json   differing keys; exit status 1 when there are any
-Environment switches and PAI_TUNE_* defaults are read once per process: one run per setting."""
+Every selection switch is a tunable; its PAI_TUNE_<name> default is read once per process: one run per setting."""
 import ctypes as C
 import hashlib
 import importlib.util
@@ -61,11 +61,12 @@ def _load_cases():
 
 
 def dump(path, register):
+    if register:
+        import torch      # before the library, as in the package: one HIP runtime for both
     L = _load("lib")
     lib = L.load()
     keep = []
     if register:
-        import torch
         for fn in (lib.pai_set_workspace, lib.pai_set_scratch, lib.pai_set_wgrad_workspace):
             keep.append(torch.zeros(REGISTER_BYTES, dtype=torch.uint8, device="cuda:0"))
             L.check(fn(keep[-1].data_ptr(), REGISTER_BYTES), "register")

@@ -120,6 +120,35 @@ def test_kernel_dispatch_table_without_gpu(pai):
         assert tuple(ops.conv_kernel_name(d, op) for op in (0, 1, 2)) == want, layer
 
 
+def test_conv_selection_switches_without_gpu(pai):
+    """The forward and weight-gradient switches of the selection are tunables: each one moves the REPORTED kernel of
+    encoders[2] (configs[1]) to the next kernel of its chain, and unsetting it brings the pinned default back.  The names
+    are those the build before this test reported under the environment switches the tunables replace."""
+    import torch
+    from thesis_pai_reconstruction_amd import ops
+    d = ops.make_desc(torch.bfloat16, 0, 64, 64, 64, 128, 0, 256, 2, 0, 0)
+    names = lambda: tuple(ops.conv_kernel_name(d, op) for op in (0, 1, 2))
+    big, tile, wg3 = "gg_fwd_patch_k<256, 128, true>", "gg_fwd_mfma_k<128, 128, false, false, 64>", "gg_wgrad_patch3_k<128, 64, 16>"
+    default = (big, big, wg3)
+    cases = [
+        ({"fwd_patch": 0}, (tile, tile, wg3), 512),
+        ({"fwd_patch256": 0}, ("gg_fwd_patch_k<128, 128, true>",) * 2 + (wg3,), 512),
+        ({"wgrad3": 0}, (big, big, "gg_wgrad_patch_k<128>"), 256),
+        ({"wgrad3": 0, "wgrad_patch": 0}, (big, big, "gg_wgrad_mfma_k<128>"), 256),
+    ]
+    assert names() == default and ops.conv_fwd_stats_rows(d) == 256
+    for switches, want, rows in cases:
+        try:
+            for k, v in switches.items():
+                ops.set_tunable(k, v)
+            assert names() == want, switches
+            assert ops.conv_fwd_stats_rows(d) == rows, switches     # 64 x 32 x 32 pixels in 128- / 256-row tiles
+        finally:
+            for k in switches:
+                ops.set_tunable(k)
+        assert names() == default and ops.conv_fwd_stats_rows(d) == 256, switches
+
+
 def test_mha_kernel_selection_without_gpu(pai):
     """Which attention kernels pai_mha_fwd / pai_mha_bwd launch is host logic (pai_mha_kernel_name reads the selection the
     launchers branch on): the matrix cores for bf16, S <= 32, head dim a multiple of 32 up to 512, unless the tunable

@@ -44,6 +44,8 @@ static int g_ntunables = 0;
 
 // Default of a tunable from the environment: PAI_TUNE_<name>=<int> (looked up once per name).  For whole-suite A/B runs
 // (pytest, bench.py) of a kernel-selection switch without touching the callers; pai_set_tunable still wins.
+// The code reads 41 tunable names; the cache holds 48 (past that a lookup still works, but calls getenv on every read)
+// and the set table above 32 at a time.
 struct TunableEnv { char name[32]; int has, value; };
 static TunableEnv g_tunable_env[48];
 static int g_ntunable_env = 0;
@@ -84,23 +86,6 @@ extern "C" int pai_set_tunable(const char* name, int value) {
     strcpy(g_tunables[g_ntunables].name, name);
     g_tunables[g_ntunables++].value = value;
     return 0;
-}
-
-// Environment switches of the selection code.  The rule: read ONCE per process (every script sets them before it starts),
-// so that a launcher and the query that reports on it cannot see two values.
-int env_int(const char* name, int def) {
-    static struct { const char* name; int value; } seen[16];
-    static int nseen = 0;
-    for (int i = 0; i < nseen; ++i)
-        if (!strcmp(seen[i].name, name)) return seen[i].value;
-    const char* e = getenv(name);
-    const int v = e ? atoi(e) : def;
-    if (nseen < 16) {
-        seen[nseen].name = name;     // (callers pass string literals)
-        seen[nseen].value = v;
-        ++nseen;                     // (published last, as the tunables above)
-    }
-    return v;
 }
 
 static void finish_gg(GG* g);

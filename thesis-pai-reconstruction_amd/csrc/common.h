@@ -232,8 +232,6 @@ int launch_fwd_simt(int dtype, const GG& g, const FwdArgs& a, hipStream_t s);
 int launch_fwd_rowdot(int dtype, const GG& g, const FwdArgs& a, hipStream_t s);
 // run-time tunables (pai_set_tunable): kernel-selection switches for A/B timing and for tests that pin a kernel
 int pai_tunable(const char* name, int def);
-// environment switch of the selection code (PAI_FWD_MODE, PAI_NO_PATCH, ...): read ONCE per process, set it before the start
-int env_int(const char* name, int def);
 // Selection inside a matrix-core family (gg_mfma.hip, gg_wg3.hip): ONE function decides the variant, its rocprofv3 symbol
 // and the launch geometry; the launcher switches on `variant`, every query (name, rows, bytes) reads a field.
 struct MfmaPlan {

@@ -26,8 +26,6 @@
 // (models/pix2pix.py:58-111), DiscriminatorBlock 1-3 (models/wrapper.py:229-232), the 1 x 1 / 3 x 3 convolutions and
 // nn.Linear layers of the other families (models/attention_unet.py:72-84, models/res_unet.py:147-163,
 // models/trans_unet.py:143-156) and their aten::convolution_backward calls.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "gg_tile.h"
@@ -46,35 +44,25 @@ bool fwd_mfma_ok(int dtype, const GG& g, const FwdArgs& a) {
 }
 
 // Tile configuration of one launch.  L2 -> LDS fill bandwidth (~70 GB/s per CU) is what bounds this
-// kernel, so the tile is made as large as the problem allows: 256 x 128 (85 FLOP per staged byte,
-// double-buffered, one 512-thread workgroup per CU) when that still gives every CU a workgroup,
-// else 128 x 128 / 128 x 64 (single buffer, 3-4 workgroups per CU), split over K when even that
-// leaves CUs idle.
+// kernel: 128 x 128 where the channels allow it, else 128 x 64 (single buffer, 3-4 workgroups per CU),
+// split over K when that leaves CUs idle.
+// (256 x 128 double-buffered, 128 x 128 double-buffered and 128 x 128 with 32-row waves were measured 5-10 % slower and
+// are no longer instantiated: HISTORY.md section 4, "One LDS stage".)
 // (A 128 x 64 wave-tile form of the 256-row kernel, gg_fwd_patchw_k / tunable fwd_wide, lived here in rounds 3-4: 5-9 %
 // faster when a launch has the GPU to itself, 1 % slower over the step -- beside the weight-gradient stream a CU holds one
 // forward workgroup, and eight 64 x 64 waves hide more latency than four 128 x 64 ones.  Removed in round 5; the body
 // still takes WPX = 128.)
-struct FwdCfg { int bm, bn, ksplit; };
+struct FwdCfg { int bn, ksplit; };   // the tile is 128 rows x bn channels
 
 static FwdCfg fwd_cfg(const GG& g) {
     FwdCfg c;
     c.bn = ((g.Cout % 128) == 0 && (g.D2 == 0 || (g.D1 % 128) == 0)) ? 128 : 64;
-    c.bm = 128;
     c.ksplit = 1;
     const int ntiles = g.Cout / c.bn;
     const int niter = g.ntaps * g.Cin / MBK;
-    const int mode = env_int("PAI_FWD_MODE", 0);
-    if (mode == 1 && c.bn == 128 && (int64_t)cdiv(g.M, 256) * ntiles * g.nphase >= 256 && niter >= 4) {
-        c.bm = 256;
-        return c;
-    }
-    if (mode == 2 && c.bn == 128 && (int64_t)cdiv(g.M, 128) * ntiles * g.nphase >= 512 && niter >= 4) {
-        c.bm = -128;   // 128 x 128, double-buffered
-        return c;
-    }
     const int tiles = cdiv(g.M, 128) * ntiles * g.nphase;
     if (tiles >= 768 || niter < 8) return c;
-    const int fixed = pai_tunable("fwd_ksplit", env_int("PAI_FWD_KSPLIT", 0));
+    const int fixed = pai_tunable("fwd_ksplit", 0);
     if (fixed > 0) {
         int ks = fixed > niter / 2 ? niter / 2 : fixed;
         while (ks > 1 && (niter % ks)) --ks;
@@ -544,8 +532,8 @@ __global__ __launch_bounds__(256) void splitk_finish_k(GG g, FwdArgs a, const fl
 
 // rows per workgroup of the patch-resident kernel for this problem: 0 (not applicable), 128 or 256 (then *pg is its geometry)
 static int patch_rows(const GG& g, const FwdCfg& c, PatchGeo* pg) {
-    const bool no_256 = env_int("PAI_NO_PATCH256", 0) != 0;
-    if (env_int("PAI_NO_PATCH", 0) || c.ksplit > 1 || c.bm != 128) return 0;
+    const bool no_256 = !pai_tunable("fwd_patch256", 1);      // 0: no 16 x 16 tiles
+    if (!pai_tunable("fwd_patch", 1) || c.ksplit > 1) return 0;   // fwd_patch 0: the tile kernels
     // the kernel addresses its sources with 32-bit byte offsets into buffer descriptors
     if ((int64_t)g.N * g.H * g.W * (g.C1 > g.C2 ? g.C1 : g.C2) * 2 >= (1ll << 31) || (int64_t)g.Cout * g.wtaps * g.Cin * 2 >= (1ll << 31))
         return 0;
@@ -1087,28 +1075,21 @@ template <int BM, int BN, bool DBB>
 __global__ __launch_bounds__(BM, 3) void gg_fwd_patch1_k(GG g, FwdArgs a, PatchGeo pg, int mtiles, int ntiles) {
     gg_fwd_patch_body<BM, BN, DBB, 1>(g, a, pg, mtiles, ntiles);
 }
-static size_t fwd_lds_bytes(int bm, int bn, bool db, int wr) {
+static size_t fwd_lds_bytes(int bm, int bn, bool db) {
     const size_t main_loop = (size_t)(db ? 2 : 1) * (bm * 128 + bn * 128);
-    const size_t epilogue = bm * (bn * 2 + 16) + (bm / wr * 2) * 2 * bn * sizeof(float);   // staged tile + [waves][2][BN]
+    const size_t epilogue = bm * (bn * 2 + 16) + (bm / 64 * 2) * 2 * bn * sizeof(float);   // staged tile + [waves][2][BN]
     return main_loop > epilogue ? main_loop : epilogue;
 }
 
 // The variants of the family: X(id, argument form, kernel, template arguments).  The reported name IS the rocprofv3 symbol,
 // spelled from the same line the launch is instantiated from.
 #define FWD_MFMA_VARIANTS(X)                                         \
-    X(FWD_TILE256_DB, TILE, gg_fwd_mfma_k, 256, 128, false, true, 64)    \
-    X(FWD_TILE128_DB, TILE, gg_fwd_mfma_k, 128, 128, false, true, 64)    \
-    X(FWD_TILE128_W32, TILE, gg_fwd_mfma_k, 128, 128, false, false, 32)  \
     X(FWD_SPLITK128_DB, TILE, gg_fwd_mfma_k, 128, 128, true, true, 64)   \
     X(FWD_SPLITK128, TILE, gg_fwd_mfma_k, 128, 128, true, false, 64)     \
     X(FWD_SPLITK64, TILE, gg_fwd_mfma_k, 128, 64, true, false, 64)       \
-    X(FWD_PATCH1_256_DBB, PATCH, gg_fwd_patch1_k, 256, 64, true)         \
     X(FWD_PATCH1_256, PATCH, gg_fwd_patch1_k, 256, 64, false)            \
     X(FWD_PATCH256_DBB, PATCH, gg_fwd_patch_k, 256, 128, true)           \
-    X(FWD_PATCH256, PATCH, gg_fwd_patch_k, 256, 128, false)              \
     X(FWD_PATCH128_DBB, PATCH, gg_fwd_patch_k, 128, 128, true)           \
-    X(FWD_PATCH128, PATCH, gg_fwd_patch_k, 128, 128, false)              \
-    X(FWD_PATCH128N_DBB, PATCH, gg_fwd_patch_k, 128, 64, true)           \
     X(FWD_PATCH128N, PATCH, gg_fwd_patch_k, 128, 64, false)              \
     X(FWD_TILE128, TILE, gg_fwd_mfma_k, 128, 128, false, false, 64)      \
     X(FWD_TILE64, TILE, gg_fwd_mfma_k, 128, 64, false, false, 64)
@@ -1126,38 +1107,33 @@ MfmaPlan fwd_mfma_plan(const GG& g) {
     // the split actually used: only when the registered workspace holds the slabs
     if (c.ksplit > 1 && (pai_ctx()->workspace == nullptr || pai_ctx()->workspace_bytes < p.workspace_bytes)) c.ksplit = 1;
     p.ksplit = c.ksplit;
-    p.bm = abs(c.bm);
+    p.bm = 128;
     p.bn = c.bn;
     p.mtiles = cdiv(g.M, p.bm);
     p.ntiles = g.Cout / c.bn;
     const int prow = patch_rows(g, c, &p.pg);
-    // statistics rows per phase: one per row tile, the split-K finish one per FIN_ROWS rows.  (PAI_FWD_MODE=3, a timing
-    // experiment, keeps reporting the rows of the patch kernel it displaces -- as before this function existed.)
+    // statistics rows per phase: one per row tile, the split-K finish one per FIN_ROWS rows
     p.rows = c.ksplit > 1 ? cdiv(g.M, FIN_ROWS) : (prow == 256 ? g.M / 256 : p.mtiles);
-    int wr = 64, waves = 0;         // waves > 0: a patch kernel
+    int waves = 0;                  // waves > 0: a patch kernel
     bool db = false;
-    // second weight-tile buffer: pays on the 128-wide tiles (bit 0: 256-row, bit 1: 128-row), not on the
-    // 64-wide ones (bit 2), whose 8 KB weight tile is cheap to wait for and which lose a workgroup per CU to it
-    const int dbb = env_int("PAI_PATCH_DBB", 3);
     size_t patch_bytes = 0;
-    if (c.bm == 256) { p.variant = FWD_TILE256_DB; db = true; }
-    else if (c.bm == -128) { p.variant = FWD_TILE128_DB; db = true; }
-    else if (c.bn == 128 && c.ksplit == 1 && env_int("PAI_FWD_MODE", 0) == 3) { p.variant = FWD_TILE128_W32; wr = 32; }
-    else if (c.ksplit > 1) {
+    if (c.ksplit > 1) {
         // two LDS stages (counted vmcnt + raw barrier): these launches have few workgroups and a long K loop per
         // workgroup, i.e. nobody else hides their L2 -> LDS latency (encoders[4] forward 50 -> 45 us, decoders[3]
         // input gradient 83 -> 76 us, scripts/micro/convbench)
         db = c.bn == 128 && pai_tunable("fwd_splitk_db", 1);
         p.variant = c.bn == 64 ? FWD_SPLITK64 : (db ? FWD_SPLITK128_DB : FWD_SPLITK128);
     } else if (prow == 256 && c.bn == 64) {
-        db = (dbb & 4) != 0; waves = 4; patch_bytes = PatchDims<256, 1>::BYTES;
-        p.variant = db ? FWD_PATCH1_256_DBB : FWD_PATCH1_256;
+        waves = 4; patch_bytes = PatchDims<256, 1>::BYTES;
+        p.variant = FWD_PATCH1_256;
     } else if (prow == 256) {
-        db = (dbb & 1) != 0; waves = 8; patch_bytes = PatchDims<256>::BYTES;
-        p.variant = db ? FWD_PATCH256_DBB : FWD_PATCH256;
+        db = true; waves = 8; patch_bytes = PatchDims<256>::BYTES;
+        p.variant = FWD_PATCH256_DBB;
     } else if (prow == 128) {
-        db = (dbb & (c.bn == 128 ? 2 : 4)) != 0; waves = 4; patch_bytes = PatchDims<128>::BYTES;
-        p.variant = c.bn == 128 ? (db ? FWD_PATCH128_DBB : FWD_PATCH128) : (db ? FWD_PATCH128N_DBB : FWD_PATCH128N);
+        // second weight-tile buffer: pays on the 128-wide tiles (256- and 128-row), not on the 64-wide ones, whose
+        // 8 KB weight tile is cheap to wait for and which lose a workgroup per CU to it
+        db = c.bn == 128; waves = 4; patch_bytes = PatchDims<128>::BYTES;
+        p.variant = db ? FWD_PATCH128_DBB : FWD_PATCH128N;
     } else p.variant = c.bn == 128 ? FWD_TILE128 : FWD_TILE64;
     p.db = db;
     p.name = fwd_mfma_names[p.variant];
@@ -1169,8 +1145,8 @@ MfmaPlan fwd_mfma_plan(const GG& g) {
         const size_t epi = prow * ((size_t)c.bn * 2 + 16) + waves * 2 * c.bn * sizeof(float);
         p.lds = lds > epi ? lds : epi;
     } else {
-        p.block = p.bm / wr * 128;
-        p.lds = fwd_lds_bytes(p.bm, c.bn, db, wr);
+        p.block = p.bm / 64 * 128;
+        p.lds = fwd_lds_bytes(p.bm, c.bn, db);
     }
     p.grid = p.mtiles * p.ntiles * g.nphase * c.ksplit;
     return p;
@@ -1193,15 +1169,12 @@ int launch_fwd_mfma(const GG& g, const FwdArgs& a, const MfmaPlan& p, hipStream_
     PAI_LAUNCH_CHECK();
     return 0;
 }
-// > 64 KB of dynamic LDS needs an explicit opt-in, once per device: the kernels on 256-row tiles
+// > 64 KB of dynamic LDS needs an explicit opt-in, once per device: the patch kernel on 256-row, 128-channel tiles
 static int fwd_lds_opt_in() {
     static PerDeviceOnce attr_set;
     if (!attr_set.first()) return 0;
-    const void* fns[3] = {reinterpret_cast<const void*>(&gg_fwd_mfma_k<256, 128, false, true>),
-                          reinterpret_cast<const void*>(&gg_fwd_patch_k<256, 128, true>),
-                          reinterpret_cast<const void*>(&gg_fwd_patch_k<256, 128, false>)};
-    hipError_t e = hipFuncSetAttribute(fns[0], hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwd_lds_bytes(256, 128, true, 64));
-    for (int i = 1; i < 3 && e == hipSuccess; ++i) e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gg_fwd_patch_k<256, 128, true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     PAI_CHECK(e == hipSuccess, "hipFuncSetAttribute(max dynamic LDS): %s", hipGetErrorString(e));
     return 0;
 }
@@ -1918,7 +1891,7 @@ static bool wgrad_patch_shape_ok(const GG& g) {
 }
 
 static bool wgrad_mfma_uses_patch(const GG& g, PatchGeo* pg) {
-    return !env_int("PAI_NO_WPATCH", 0) && wgrad_patch_shape_ok(g) && patch_geo(g, 4, pg);
+    return pai_tunable("wgrad_patch", 1) && wgrad_patch_shape_ok(g) && patch_geo(g, 4, pg);
 }
 
 // 128-channel tiles unless the layer would then run as at most one un-split workgroup per CU (the bottleneck layers:
@@ -1939,7 +1912,6 @@ static int wgrad_mfma_splits(const GG& g, bool patch, int tiles, int* rows_out) 
     // Split of the pixel range: enough workgroups to fill the chip (3 per CU for the 128-wide tile, 4 for the
     // lighter 64-wide one), but every split adds one fp32 atomic pass over dW -- for the small-image layers
     // that pass, not the MFMA loop, is the cost, so a split never gets fewer than 512 pixels.
-    const int target_env = env_int("PAI_WGRAD_TARGET", 0);
     const int target_tun = pai_tunable("wgrad_target", 0);
     // gg_wgrad_patch_k fits four workgroups per CU (128 VGPRs), gg_wgrad_mfma_k<128> three.  Measured per layer
     // (scripts/micro/convbench --set wgrad_target=...): the 137-GFLOP layers (decoders[4-6], D blocks 1-3 at 2N) want
@@ -1948,15 +1920,15 @@ static int wgrad_mfma_splits(const GG& g, bool patch, int tiles, int* rows_out) 
     // the extra atomic passes over dW cost more than the better balance buys.
     const double gflop = 2.0 * (double)g.M * g.nphase * g.Cout * g.ntaps * g.Cin * 1e-9;
     const int target_def = (patch && gflop >= 100.0) ? 1024 : 512;
-    const int target = target_tun ? target_tun : (target_env ? target_env : target_def);
+    const int target = target_tun ? target_tun : target_def;
     int splits = cdiv(target, tiles);
-    const int max_splits = cdiv(g.M, env_int("PAI_WGRAD_MINROWS", 512));
+    const int max_splits = cdiv(g.M, pai_tunable("wgrad_minrows", 512));
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     // An un-split launch owns every dW element in exactly one workgroup and updates it with a plain
     // read-modify-write; a split one adds splits x |dW| bytes of float atomics (~1.3 TB/s chip-wide).  For the
     // bottleneck layers (<= 2048 pixels, 4-8 M weights) those atomics were the whole cost.
-    const int unsplit_rows = env_int("PAI_WGRAD_UNSPLIT_ROWS", 2048);
+    const int unsplit_rows = pai_tunable("wgrad_unsplit_rows", 2048);
     if ((tiles >= 256 && g.M <= unsplit_rows) || (tiles >= 512 && g.M <= 2 * unsplit_rows)) splits = 1;
     int rows = cdiv(cdiv(g.M, splits), 64) * 64;
     splits = cdiv(g.M, rows);

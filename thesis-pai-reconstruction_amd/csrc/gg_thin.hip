@@ -12,8 +12,6 @@
 //                                 out[2a+ph][2b+pw][t] = bias + sum of 4 Y entries     (col2im)
 //   TW  thin weight gradient      D[k][wc]    = sum_pix patch[pix][k] * wide[pix][wc] (K = pixels)
 // patch[pix][k=(tap,t)] = thin_t[n][S*gy + dy[tap]][S*gx + dx[tap]] (zero outside the image).
-#include <stdlib.h>
-
 #include "common.h"
 
 #ifndef THIN_ABL
@@ -547,7 +545,7 @@ static void launch_thin_fwd2(const GG& g, const FwdArgs& a, int blocks, hipStrea
 
 static int thin_fwd_blocks(const GG& g) {
     int blocks = cdiv(g.M, 64);
-    static const int cap = getenv("PAI_TF_BLOCKS") ? atoi(getenv("PAI_TF_BLOCKS")) : 4096;
+    const int cap = pai_tunable("thin_fwd_blocks", 4096);
     return blocks > cap ? cap : blocks;
 }
 
@@ -1216,8 +1214,8 @@ bool thin_wgrad_convt_ok(int dtype, const GG& g) {
 
 // workgroups along the pixel range; with the two-stage reduction more of them cost nothing
 static int tw_blocks(int64_t M, int groups, bool two_stage) {
-    static const int cap_env = getenv("PAI_TW_BLOCKS") ? atoi(getenv("PAI_TW_BLOCKS")) : 0;
-    int cap = cap_env ? cap_env : (two_stage ? 1024 / groups : 512);   // ~4 workgroups per CU over all channel groups
+    const int cap_tun = pai_tunable("thin_wgrad_blocks", 0);      // 0: the built-in rule
+    int cap = cap_tun ? cap_tun : (two_stage ? 1024 / groups : 512);   // ~4 workgroups per CU over all channel groups
     if (cap < 64) cap = 64;
     const int chunks = cdiv(M, 64);
     int blocks = chunks < cap ? chunks : cap;
@@ -1244,7 +1242,7 @@ static int launch_tw(ThinW& p, int T, hipStream_t s) {
     const int chunks = cdiv(p.M, p.pair ? 128 : 64);
     const int groups = cdiv(p.WC1 + p.WC2, 128);
     const int64_t need = thin_wgrad_scratch_bytes(p.M, T, p.WC1 + p.WC2);
-    static const bool no_two = getenv("PAI_TW_ATOMIC") && atoi(getenv("PAI_TW_ATOMIC")) != 0;
+    const bool no_two = pai_tunable("thin_wgrad_atomic", 0) != 0;   // 1: never two-stage
     const pai_handle_s* ctx = pai_ctx();
     const bool two_stage = !no_two && ctx->scratch != nullptr && ctx->scratch_bytes >= need;
     int blocks = tw_blocks(p.M, groups, two_stage);
