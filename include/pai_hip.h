@@ -66,7 +66,9 @@ const char* pai_last_error(void);
  * the multi-tensor calls (pai_adam_multi, pai_adam_multi_dev, pai_zero_multi, pai_lerp_multi) accept NULL for a tensor of 0 elements.
  * 138: differentiable spatial attention (pai_sattn_fwd_lse, pai_sattn_bwd, pai_sattn_kernel_name).
  * 139: train-mode FiLM norm (pai_film_norm_fwd, pai_film_norm_bwd, pai_film_norm_ws_floats, pai_film_norm_slabs); PAI_ACT_SILU
- * is also taken by these. */
+ * is also taken by these.
+ * 140: the PatchGAN head with its loss in one launch (pai_head_loss, pai_head_loss_ok); fp32 input gradient with an addend
+ * (pai_conv_dgrad_f32add, pai_conv_dgrad_f32add_ok); tunables "head_fused", "head_loss_rg". */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -220,6 +222,16 @@ int pai_conv_fwd(const pai_conv_desc* d, const void* x1, const void* x2, const v
  * only -- the generator image in Discriminator.forward, models/wrapper.py:237). */
 int pai_conv_dgrad(const pai_conv_desc* d, const void* dy, const void* w_dgrad, void* dx1,
                    void* dx2, int only_c2, void* stream);
+
+/* pai_conv_dgrad(only_c2) as fp32 with an fp32 addend in the store:
+ *   dx2_f32[i] = float(bf16(conv_backward_input(dy, w)[:, C1:][i])) + addend[i]
+ * -- the bits that pai_conv_dgrad into a bf16 tensor, pai_cast to fp32 and pai_add_act leave, without the two passes over
+ * the image (the discriminator's gradient w.r.t. the generated image plus the L1 term, models/wrapper.py:44-50).  Taken by
+ * the bf16 (1 | 1)-channel k4 s2 first layer with H, W multiples of 32 (thin_up_k); pai_conv_dgrad_f32add_ok answers
+ * 1 / 0 on the host (0 too when the tunable "head_fused" is 0), the call itself refuses every other layer. */
+int pai_conv_dgrad_f32add_ok(const pai_conv_desc* d);
+int pai_conv_dgrad_f32add(const pai_conv_desc* d, const void* dy, const void* w_dgrad, const float* addend,
+                          float* dx2_f32, void* stream);
 
 /* pai_conv_dgrad followed by the activation backward of the layer that produced x1, in one pass:
  *   dx1 = act1'(a1) * conv_backward_input(dy, w)[:, :C1],  dx2 as pai_conv_dgrad
@@ -532,6 +544,27 @@ int pai_l1(const float* pred, const float* target, int64_t numel, float loss_sca
            float grad_scale, float* grad, void* stream);
 int pai_mse(const float* pred, const float* target, int64_t numel, float loss_scale, double* loss,
             float grad_scale, float* grad, void* stream);
+/* The PatchGAN head (bias-free Conv2d(C, 1, k4, s1, p1), models/wrapper.py:233) with the loss on its logits in ONE launch
+ * (head_loss_k), per image:
+ *   logits[n]  = conv(a3[n], w)                                   fp32 [N][H-1][W-1], as pai_conv_fwd(y_f32) gives them
+ *   t, numel   = (target_first, n_first * (H-1)(W-1)) for n < n_first, (target_rest, (N - n_first) * (H-1)(W-1)) otherwise
+ *                (n_first is clamped to [0, N]: n_first >= N means one target for the whole batch)
+ *   *loss     += loss_scale / numel * sum BCE-with-logits(logits[n], t)      fp64, one atomic per image
+ *                (each image's term is rounded to a multiple of 2^-36 while it is below 256: the fp64 additions are then exact
+ *                and the value does not depend on the order in which the atomics arrive)
+ *   dl, dl_f32 = grad_scale / numel * (sigmoid(logits[n]) - t)     bf16 / fp32, either may be NULL
+ *   du[n]      = act'(act_src[n]) * bf16(conv_backward_input(dl[n], w))      bf16 [N][H][W][C] or NULL (then w_dgrad,
+ *                act_src may be NULL); act_src is the stored activation the head read (a3), act as pai_conv_dgrad_act
+ * d: the head's forward descriptor; w_fwd / w_dgrad: its two packs.  logits, dl and du carry the bits of
+ * pai_conv_fwd -> pai_bce_logits (once per half) -> pai_cast -> pai_conv_dgrad_act; the loss is summed per image instead of
+ * per half and differs from theirs by less than an ulp of its fp32 value.  pai_head_loss_ok (host only, as the *_kernel_name queries): 1 when the launch takes the layer -- bf16, no
+ * bias, Cout = 1, C2 = 0, C = 32 * {1, 2, 4, 8, 16}, no ReLU-on-load / epilogue activation, and an image whose tap values fit
+ * the 96 KB of LDS the kernel asks for (17 * 4 B per pixel + 32 B per channel: 32 x 32 pixels at C = 512) -- and the tunable
+ * "head_fused" is not 0.  Tunable "head_loss_rg" (default 4): workgroups per image when du is written. */
+int pai_head_loss_ok(const pai_conv_desc* d, int has_bias);
+int pai_head_loss(const pai_conv_desc* d, const void* a3, const void* w_fwd, const void* w_dgrad, int n_first,
+                  float target_first, float target_rest, float loss_scale, double* loss, float grad_scale,
+                  float* logits, void* dl, float* dl_f32, void* du, const void* act_src, int act, void* stream);
 /* *out = (float)*acc; *acc = 0.  The fp64 accumulator a group of loss launches added into becomes the fp32 loss value
  * and is re-armed for the next step in one single-thread launch (the reference sums fp32 scalars with tensor ops,
  * models/wrapper.py:50,94). */

@@ -14,7 +14,7 @@ void pai_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* pai_last_error(void) { return g_err; }
-extern "C" int pai_version(void) { return 139; }   // 110: handles, tunables, device-side Adam step, *_take, pack multi; 120: weight-gradient workspace; 121: pai_adam_pack, pai_bn_bwd_apply_affine; 130: launch plans; 131: pai_lerp_multi; 132: input prologue (pai_conv_fwd_pro / pai_conv_wgrad_pro); 133: device-resident data set (data.hip); 134: report evaluation (eval.hip); 135: Palette sampling (palette.hip); 136: pai_mha_kernel_name; 137: denormalize keeps NaN, empty tensors in the multi-tensor calls; 138: differentiable spatial attention; 139: train-mode FiLM norm (film_norm.hip)
+extern "C" int pai_version(void) { return 140; }   // 110: handles, tunables, device-side Adam step, *_take, pack multi; 120: weight-gradient workspace; 121: pai_adam_pack, pai_bn_bwd_apply_affine; 130: launch plans; 131: pai_lerp_multi; 132: input prologue (pai_conv_fwd_pro / pai_conv_wgrad_pro); 133: device-resident data set (data.hip); 134: report evaluation (eval.hip); 135: Palette sampling (palette.hip); 136: pai_mha_kernel_name; 137: denormalize keeps NaN, empty tensors in the multi-tensor calls; 138: differentiable spatial attention; 139: train-mode FiLM norm (film_norm.hip); 140: pai_head_loss (head.hip), pai_conv_dgrad_f32add
 
 // build-option bits; none since ABI 130 (bit 0 announced the round-2 experiment kernels, which were removed)
 extern "C" int pai_build_flags(void) { return 0; }
@@ -644,6 +644,28 @@ extern "C" int pai_conv_dgrad(const pai_conv_desc* d, const void* dy, const void
     a.y1 = dx1; a.y2 = dx2;
     a.skip_d1 = only_c2;
     return run_fwd(d->dtype, g, a, (hipStream_t)stream);
+}
+
+// The only_c2 input gradient as fp32 with an fp32 addend in the store (thin_up_k): what pai_conv_dgrad into a bf16 tensor, a
+// cast to fp32 and pai_add_act leave, in one launch.  tunable "head_fused" = 0 answers "no" (the three launches run).
+extern "C" int pai_conv_dgrad_f32add_ok(const pai_conv_desc* d) {
+    GG g;
+    if (!d || gg_build_dgrad(d, &g)) return 0;
+    return pai_tunable("head_fused", 1) && thin_up_f32add_ok(d->dtype, g) ? 1 : 0;
+}
+
+extern "C" int pai_conv_dgrad_f32add(const pai_conv_desc* d, const void* dy, const void* w_dgrad, const float* addend,
+                                     float* dx2_f32, void* stream) {
+    GG g;
+    if (gg_build_dgrad(d, &g)) return 1;
+    PAI_CHECK(dy && w_dgrad && addend && dx2_f32, "pai_conv_dgrad_f32add: null pointer");
+    PAI_CHECK(thin_up_f32add_ok(d->dtype, g), "pai_conv_dgrad_f32add: not a bf16 (1 | 1)-channel k4 s2 layer on thin_up_k (ask pai_conv_dgrad_f32add_ok)");
+    FwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x1 = dy; a.w = w_dgrad;
+    a.yf32 = dx2_f32; a.badd = addend;
+    a.skip_d1 = 1;
+    return launch_thin_dgrad(g, a, (hipStream_t)stream);
 }
 
 extern "C" int pai_conv_dgrad_act(const pai_conv_desc* d, const void* dy, const void* w_dgrad,

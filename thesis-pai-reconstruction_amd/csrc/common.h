@@ -297,6 +297,7 @@ bool head_dgrad_ok(int dtype, const GG& g, const FwdArgs& a);
 int launch_head_dgrad(const GG& g, const FwdArgs& a, hipStream_t s);
 int thin_fwd_bwd_rows(int dtype, const GG& g, const FwdArgs& a, int act1, const void* add, const float* scale);
 int launch_thin_dgrad(const GG& g, const FwdArgs& a, hipStream_t s);
+bool thin_up_f32add_ok(int dtype, const GG& g);
 
 struct WgradArgs {
     const void *x1, *x2, *dy;

@@ -874,6 +874,15 @@ __global__ __launch_bounds__(256) void thin_up_k(GG g, FwdArgs a, int t0, int ti
                 const int hy = hy0 + (int)(signed char)(e & 0xff), hx = hx0 + (int)(signed char)((e >> 8) & 0xff);
                 v += Ys[tt][hy * TU_HW + hx][(e >> 16) & 0xff];
             }
+            if (a.badd) {
+                // pai_conv_dgrad_f32add: the D2 part as fp32 with an fp32 addend -- the value a bf16 store, a cast to fp32
+                // and an add would leave (the bf16 rounding is kept), without the two passes over the image
+                if (t >= g.D1) {
+                    const size_t idx = o * g.D2 + (t - g.D1);
+                    a.yf32[idx] = bf2f(f2bf(v)) + ((const float*)a.badd)[idx];
+                }
+                continue;
+            }
             if (t < g.D1) {
                 if (a.y1 && !a.skip_d1) ((bf16_t*)a.y1)[o * g.D1 + t] = f2bf(v);
             } else if (a.y2) {
@@ -891,6 +900,11 @@ __global__ __launch_bounds__(256) void thin_up_k(GG g, FwdArgs a, int t0, int ti
 static bool thin_up_ok(const GG& g) {
     return pai_tunable("thin_up", 1) && g.nphase == 4 && g.ntaps == 4 && g.OS == 2 && g.wtaps == 16 && (g.H % 16) == 0 &&
            (g.W % 16) == 0 && (g.Cin == 64 || g.Cin == 128);
+}
+
+// pai_conv_dgrad_f32add: the only_c2 input gradient of a (1 | 1)-channel first layer on thin_up_k (D block 0)
+bool thin_up_f32add_ok(int dtype, const GG& g) {
+    return thin_dgrad_shape_ok(dtype, g) && thin_up_ok(g) && g.Cout == 2 && g.D1 == 1 && g.D2 == 1;
 }
 
 int launch_thin_dgrad(const GG& g, const FwdArgs& a, hipStream_t s) {

@@ -927,7 +927,7 @@ class DiscEngine:
         ops.cast(t, dst)
         return dst
 
-    def forward(self, x, y, dtype, y2=None):
+    def forward(self, x, y, dtype, y2=None, head: bool = True):
         """y2: a second image batch evaluated against the same conditioning x in the same pass -- the rows of the
         2N-sample batch are [x|y] then [x|y2] (what ``cat([x, x]), cat([y, y2])`` would feed), written straight into
         the engine's input buffers without materialising the concatenations."""
@@ -962,10 +962,53 @@ class DiscEngine:
         for k in range(1, 4):
             wf, _ = self.packs[k].get(dtype)
             ops.conv_fwd(P["desc"][k], S["a"][k - 1], None, wf, self.convs[k].bias, y_act=S["a"][k])
+        S["head_done"] = False
+        if not head:
+            return None, S
         wf, _ = self.packs[4].get(dtype)
         S["logits"] = torch.empty_like(S["logits"])    # owned by the caller, see UnetEngine.forward
         ops.conv_fwd(P["desc"][4], S["a"][3], None, wf, None, y_f32=S["logits"])
         return S["logits"], S
+
+    @staticmethod
+    def fused_enabled() -> bool:
+        """PAI_HEAD_FUSED=0: the head, its loss and the fp32 input gradient run as the separate launches they were (read per
+        call: the A/B of the fused launches and the tests that compare the two paths)."""
+        return os.environ.get("PAI_HEAD_FUSED", "1") not in ("", "0")
+
+    def head_fused_ok(self, dtype) -> bool:
+        """``forward_loss`` can run: bf16 storage and a head ``pai_head_loss`` takes (``forward_loss`` asks the library about the shape)."""
+        return dtype == torch.bfloat16 and self.fused_enabled() and self.convs[4].bias is None
+
+    def _grads(self, S):
+        if S["grads"] is None:
+            P = S["P"]
+            S["grads"] = {"du": [torch.empty_like(a) for a in S["a"]],
+                          "dl": torch.empty(S["logits"].numel(), dtype=P["dtype"], device=P["device"]),
+                          "dl32": torch.empty(S["logits"].numel(), dtype=torch.float32, device=P["device"]),
+                          "dy": torch.empty(P["N"] * P["H"] * P["W"] * self.in_ch, dtype=P["dtype"], device=P["device"])}
+        return S["grads"]
+
+    def forward_loss(self, x, y, dtype, y2, n_first, target_first, target_rest, acc, need_grad: bool):
+        """The forward pass with the BCE-with-logits loss of its logits against a per-image constant target (images below
+        ``n_first``: ``target_first``) added into the fp64 accumulator ``acc`` -- the head, the loss, the logit gradient and
+        (``need_grad``) the head's input gradient are ONE launch (``pai_head_loss``).  Leaves the final logit gradient for a
+        unit loss gradient in the slot's ``dl`` / ``dl32`` and ``du[3]``; ``backward(..., head_done=True)`` continues
+        from there.  Returns the slot, or None when the head is not one the launch takes (nothing has run then)."""
+        if not (x.is_cuda and y.is_cuda):
+            raise ops.PaiError("Discriminator (HIP) needs HIP device tensors; there is no CPU path")
+        N = x.shape[0] * (1 if y2 is None else 2)
+        P = self._plan(N, x.shape[2], x.shape[3], dtype, x.device)
+        if not ops.head_loss_ok(P["desc"][4], self.convs[4].bias is not None):      # (host only; reads the tunable head_fused)
+            return None
+        _, S = self.forward(x, y, dtype, y2=y2, head=False)
+        wf, wd = self.packs[4].get(dtype)
+        G = self._grads(S) if need_grad else None
+        ops.head_loss(P["desc"][4], S["a"][3], wf, wd if need_grad else None, n_first, target_first, target_rest, 1.0, acc, 1.0,
+                      S["logits"], G["dl"] if need_grad else None, G["dl32"] if need_grad else None,
+                      G["du"][3] if need_grad else None, ACT_LRELU)
+        S["head_done"] = need_grad
+        return S
 
     def _wgrad_desc(self, P, k):
         """The descriptor block k's weight gradient is launched with: PAI_HINT_SOLO -- two workgroups per CU -- in the
@@ -982,27 +1025,32 @@ class DiscEngine:
             solo[k] = d
         return solo[k]
 
-    def backward(self, S, glogits, need_params: bool, need_dy: bool, fresh: bool = False):
-        """``fresh``: see UnetEngine.backward."""
+    def backward(self, S, glogits, need_params: bool, need_dy: bool, fresh: bool = False, head_done: bool = False,
+                 addend=None):
+        """``fresh``: see UnetEngine.backward.  ``head_done``: ``forward_loss`` left the final ``dl`` and ``du[3]`` in the
+        slot (``glogits`` is ignored): the pass starts at the head's weight gradient and block 3.  ``addend`` (with
+        ``need_dy``): a contiguous fp32 tensor of the image's shape that is added to the returned gradient -- in the store
+        of block 0's input gradient where ``pai_conv_dgrad_f32add`` takes the layer, by ``pai_add_act`` otherwise."""
         conv_wgrad = ops.conv_wgrad_overwrite_w if fresh else ops.conv_wgrad
         P = S["P"]
         N, H, W, dtype, dev = P["N"], P["H"], P["W"], P["dtype"], P["device"]
-        if S["grads"] is None:
-            G = {"du": [torch.empty_like(a) for a in S["a"]],
-                 "dl": torch.empty(S["logits"].numel(), dtype=dtype, device=dev),
-                 "dy": torch.empty(N * H * W * self.in_ch, dtype=dtype, device=dev)}
-            S["grads"] = G
-        G = S["grads"]
+        G = self._grads(S)
         A = self.arena() if need_params else None
         hook = self.grad_ready_hook
-        glogits = glogits.contiguous().float()
-        if dtype == torch.float32:
-            dl = glogits.reshape(-1)
-        else:
-            ops.cast(glogits, G["dl"])
+        if head_done:
+            if not S.get("head_done"):
+                raise ops.PaiError("DiscEngine.backward(head_done=True) without a forward_loss that kept its gradients")
             dl = G["dl"]
+        else:
+            glogits = glogits.contiguous().float()
+            if dtype == torch.float32:
+                dl = glogits.reshape(-1)
+            else:
+                ops.cast(glogits, G["dl"])
+                dl = G["dl"]
         d = P["desc"][4]
         side = self._side
+        gy = None
         if need_params:
             with torch.cuda.stream(side.fork(d)):
                 ops.conv_wgrad(d, S["a"][3], None, dl, A.seg(self.convs[4].weight), None)     # thin (one output channel): added
@@ -1011,7 +1059,8 @@ class DiscEngine:
             side.mark_scratch()
         _, wd = self.packs[4].get(dtype)
         # du[k] = LeakyReLU'(a[k]) * dgrad of block k+1: the activation backward rides on the dgrad store
-        ops.conv_dgrad_act(d, dl, wd, G["du"][3], None, S["a"][3], ACT_LRELU)
+        if not head_done:
+            ops.conv_dgrad_act(d, dl, wd, G["du"][3], None, S["a"][3], ACT_LRELU)
         for k in range(3, -1, -1):
             conv = self.convs[k]
             d = P["desc"][k]
@@ -1030,14 +1079,25 @@ class DiscEngine:
                 ops.conv_dgrad_act(d, G["du"][k], wd, G["du"][k - 1], None, S["a"][k - 1], ACT_LRELU)
             elif need_dy:
                 _, wd = self.packs[0].get(dtype)
-                ops.conv_dgrad(d, G["du"][0], wd, None, G["dy"], only_c2=True)
+                if addend is not None and self.in_ch == 1 and self.fused_enabled() and addend.dtype == torch.float32 \
+                        and addend.is_contiguous() and addend.numel() == N * H * W and ops.conv_dgrad_f32add_ok(d):
+                    gy = torch.empty(N * H * W, dtype=torch.float32, device=dev)
+                    ops.conv_dgrad_f32add(d, G["du"][0], wd, addend, gy)      # fp32 + addend in the store
+                else:
+                    ops.conv_dgrad(d, G["du"][0], wd, None, G["dy"], only_c2=True)
         side.join()
         if need_params and hook is not None:
             hook(A, A.end_of(self.convs[0].bias))
         if not need_dy:
             return None
+        if gy is not None:
+            return gy.view(N, 1, H, W)
         gy = torch.empty(N * H * W * self.in_ch, dtype=torch.float32, device=dev)
         ops.cast(G["dy"], gy)
-        if self.in_ch == 1:
-            return gy.view(N, 1, H, W)
-        return gy.view(N, H, W, self.in_ch).permute(0, 3, 1, 2)
+        gy = gy.view(N, 1, H, W) if self.in_ch == 1 else gy.view(N, H, W, self.in_ch).permute(0, 3, 1, 2)
+        if addend is not None:
+            if gy.is_contiguous() and gy.numel() % 8 == 0:
+                ops.add_act(torch.float32, gy, addend, ops.ACT_NONE, gy)
+            else:
+                gy = gy + addend
+        return gy

@@ -128,6 +128,58 @@ class DiscPairsFunction(torch.autograd.Function):
         return (None,) * (5 + len(params))
 
 
+class DiscPairsLossFunction(torch.autograd.Function):
+    """``gan_discriminator_loss_pairs(DiscPairsFunction(x, y_real, y_fake), N)`` as ONE node (the discriminator phase of the
+    GAN step, reference models/wrapper.py:124-138 with the loss of :68-95): on a head ``pai_head_loss`` takes, the logits, both
+    BCE terms, the logit gradient and the head's input gradient are one launch in the forward pass, and a backward pass seeded
+    with the cached unit scalar starts at the head's weight gradient.  Any other seed scales the fp32 logit gradient and runs
+    the head's input gradient as a launch of its own; any other head (fp32 storage, a bias, an image beyond the kernel's LDS,
+    ``PAI_HEAD_FUSED=0``) runs the launches of the two separate nodes.  Only parameter gradients flow."""
+
+    @staticmethod
+    def forward(ctx, x, y_real, y_fake, engine, dtype, *params):
+        _check_f32_cuda(x, y_real, y_fake)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            raise ops.PaiError("DiscPairsLossFunction carries no gradient to its image inputs; detach them")
+        need = any(ctx.needs_input_grad[5:])
+        n = x.shape[0]
+        ent = _ACC.get(x.device, "gan_d")
+        out = torch.empty((), dtype=torch.float32, device=x.device)
+        slot = engine.forward_loss(x, y_real, dtype, y_fake, n, 1.0, 0.0, ent[0], need) if engine.head_fused_ok(dtype) else None
+        ctx.fused = slot is not None
+        grad = None
+        if slot is None:
+            logits, slot = engine.forward(x, y_real, dtype, y2=y_fake)
+            flat = logits.view(-1)
+            k = (flat.numel() // logits.shape[0]) * n
+            grad = torch.empty_like(flat) if need else None
+            ops.bce_logits(flat[:k], 1.0, 1.0, ent[0], 1.0, grad[:k] if need else None)
+            ops.bce_logits(flat[k:], 0.0, 1.0, ent[0], 1.0, grad[k:] if need else None)
+        ops.scalar_take(ent[0], out)
+        _ACC.taken(ent)
+        if need:
+            ctx.engine, ctx.ref, ctx.params = engine, _SlotRef(engine, slot), params
+            if grad is not None:
+                ctx.save_for_backward(grad)
+        else:
+            engine.release(slot)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        engine, slot, params = ctx.engine, ctx.ref.take(), ctx.params
+        arena = engine.arena()
+        fresh = arena.begin_backward(params, overwrite_weights=True)
+        if ctx.fused and _is_unit(gout):
+            engine.backward(slot, None, True, False, fresh, head_done=True)
+        else:
+            grad = slot["grads"]["dl32"] if ctx.fused else ctx.saved_tensors[0]
+            engine.backward(slot, _scaled(grad, gout).view(slot["logits"].shape), True, False, fresh)
+        arena.attach(params)
+        engine.release(slot)
+        return (None,) * (5 + len(params))
+
+
 class DiscGenLossFunction(torch.autograd.Function):
     """The generator's GAN loss in one node: ``BCE(D(x, pred), 1) + l1_weight * L1(pred, target)`` (reference
     models/wrapper.py:44-50).  ``pred`` feeds both terms; as two autograd nodes their gradients meet in an aten ``add``
@@ -140,14 +192,19 @@ class DiscGenLossFunction(torch.autograd.Function):
         _check_f32_cuda(x, pred, target)
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
             raise ops.PaiError("gradient w.r.t. the conditioning image / the target is not supported")
-        logits, slot = engine.forward(x, pred, dtype)
         pc, tc = pred.contiguous().float(), target.contiguous().float()
         need_pred, need_params = ctx.needs_input_grad[1], any(ctx.needs_input_grad[6:])
         need = need_pred or need_params
-        gl = torch.empty_like(logits) if need else None
         gp = torch.empty_like(pc) if need_pred else None
         ent = _ACC.get(pc.device, "gan_g")
-        ops.bce_logits(logits, 1.0, 1.0, ent[0], 1.0, gl)
+        # the head, BCE(logits, 1), its gradient and the head's input gradient as one launch where pai_head_loss takes the head
+        slot = engine.forward_loss(x, pred, dtype, None, x.shape[0], 1.0, 1.0, ent[0], need) if engine.head_fused_ok(dtype) else None
+        ctx.fused = slot is not None
+        gl = None
+        if slot is None:
+            logits, slot = engine.forward(x, pred, dtype)
+            gl = torch.empty_like(logits) if need else None
+            ops.bce_logits(logits, 1.0, 1.0, ent[0], 1.0, gl)
         ops.l1(pc, tc, float(l1_weight), ent[0], float(l1_weight), gp)
         out = torch.empty((), dtype=torch.float32, device=pc.device)
         ops.scalar_take(ent[0], out)
@@ -164,16 +221,25 @@ class DiscGenLossFunction(torch.autograd.Function):
     def backward(ctx, gout):
         engine, slot, params = ctx.engine, ctx.ref.take(), ctx.params
         saved = list(ctx.saved_tensors)
-        gl = _scaled(saved.pop(0), gout)
+        unit = _is_unit(gout)
+        head_done = ctx.fused and unit
+        if head_done:
+            gl = None
+        elif ctx.fused:
+            gl = _scaled(slot["grads"]["dl32"], gout).view(slot["logits"].shape)
+        else:
+            gl = _scaled(saved.pop(0), gout)
         fresh = False
         if ctx.need_params:
             arena = engine.arena()
             fresh = arena.begin_backward(params, overwrite_weights=True)
-        gy = engine.backward(slot, gl, ctx.need_params, ctx.need_pred, fresh)
+        # the unit seed: the L1 gradient is added in the store of the discriminator's input gradient where the engine can
+        addend = saved[0] if ctx.need_pred and unit and engine.fused_enabled() else None
+        gy = engine.backward(slot, gl, ctx.need_params, ctx.need_pred, fresh, head_done=head_done, addend=addend)
         if ctx.need_params:
             arena.attach(params)
         engine.release(slot)
-        if ctx.need_pred:
+        if ctx.need_pred and addend is None:
             gp = _scaled(saved.pop(0), gout)
             if gy.is_contiguous() and gy.numel() % 8 == 0:
                 ops.add_act(torch.float32, gy, gp, ops.ACT_NONE, gy)
@@ -252,6 +318,12 @@ def unit_seed(device) -> torch.Tensor:
         t = torch.ones((), dtype=torch.float32, device=device)
         _UNIT[device.index] = t
     return t
+
+
+def _is_unit(gout) -> bool:
+    """gout IS the cached unit seed of its device (the test ``_scaled`` makes)."""
+    u = _UNIT.get(gout.device.index) if gout.is_cuda else None
+    return u is not None and gout.data_ptr() == u.data_ptr()
 
 
 def _scaled(grad, gout):

@@ -83,6 +83,10 @@ SIGNATURES = {
     "pai_conv_fwd": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pai_conv_dgrad": (_I, [_D, _P, _P, _P, _P, _I, _P]),
     "pai_conv_dgrad_act": (_I, [_D, _P, _P, _P, _P, _P, _I, _P]),
+    "pai_conv_dgrad_f32add_ok": (_I, [_D]),
+    "pai_conv_dgrad_f32add": (_I, [_D, _P, _P, _P, _P, _P]),
+    "pai_head_loss_ok": (_I, [_D, _I]),
+    "pai_head_loss": (_I, [_D, _P, _P, _P, _I, _F, _F, _F, _P, _F, _P, _P, _P, _P, _P, _I, _P]),
     "pai_conv_dgrad_bn_rows_max": (_I, [_D]),
     "pai_conv_dgrad_bn": (_I, [_D, _P, _P, _P, _P, C.POINTER(BwdEpilogue), C.POINTER(_I), _P]),
     "pai_bn_bwd_finalize": (_I, [_P, _I, _I, _P, _P, _P, _P]),

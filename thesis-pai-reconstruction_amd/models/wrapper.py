@@ -144,7 +144,11 @@ class UnetWrapper(LightningModule):
             # Train discriminator.
             self.toggle_optimizer(opt_d)
             pred = pred_g.detach() if reuse else self.unet(x)
-            if getattr(self.discriminator, "supports_batched_pairs", False):
+            if pred.is_cuda and getattr(self.discriminator, "supports_fused_pairs_loss", False):
+                # forward_pairs + gan_discriminator_loss_pairs as ONE autograd node: head, both BCE terms and the head's
+                # input gradient are one launch where the head allows it (same d_loss)
+                d_loss = self.discriminator.pairs_loss(x, target, pred)
+            elif getattr(self.discriminator, "supports_batched_pairs", False):
                 # the PatchGAN has no cross-sample coupling: D(x,target) and D(x,pred) are run as
                 # one batch of 2N (one backward pass, so gradient buckets can be reduced while it runs)
                 n = x.shape[0]
@@ -245,6 +249,7 @@ class Discriminator(nn.Module):
         self.compute_dtype = torch.float32
         self.supports_batched_pairs = True
         self.supports_fused_generator_loss = True
+        self.supports_fused_pairs_loss = True
         self.discriminator = nn.Sequential(
             DiscriminatorBlock(in_channels * 2, 64, norm=False),
             DiscriminatorBlock(64, 128),
@@ -277,3 +282,10 @@ class Discriminator(nn.Module):
         eng = self.engine
         params = [p for p, _ in eng.ordered_params()]
         return PF.DiscPairsFunction.apply(x.detach(), y_real.detach(), y_fake.detach(), eng, self.compute_dtype, *params)
+
+    def pairs_loss(self, x, y_real, y_fake):
+        """``gan_discriminator_loss_pairs(forward_pairs(x, y_real, y_fake), N)`` -- BCE(D(x, y_real), 1) + BCE(D(x, y_fake), 0),
+        reference models/wrapper.py:68-95 -- as one autograd node (``PF.DiscPairsLossFunction``)."""
+        eng = self.engine
+        params = [p for p, _ in eng.ordered_params()]
+        return PF.DiscPairsLossFunction.apply(x.detach(), y_real.detach(), y_fake.detach(), eng, self.compute_dtype, *params)

@@ -351,6 +351,35 @@ def conv_dgrad_act(d, dy, w_dgrad, dx1, dx2, a1, act1):
                                             _stream()), "pai_conv_dgrad_act")
 
 
+def conv_dgrad_f32add_ok(d) -> bool:
+    """The only_c2 input gradient of this layer can be stored as fp32 with an addend (pai_conv_dgrad_f32add_ok; host only)."""
+    return bool(L.load().pai_conv_dgrad_f32add_ok(C.byref(d)))
+
+
+def conv_dgrad_f32add(d, dy, w_dgrad, addend, dx2_f32):
+    """dx2_f32 = float(bf16(dgrad[:, C1:])) + addend: conv_dgrad(only_c2) -> cast -> add_act in one launch, same bits."""
+    with _Timed(d, 1):
+        L.check(L.load().pai_conv_dgrad_f32add(C.byref(d), _p(dy), _p(w_dgrad), _p(addend, torch.float32),
+                                               _p(dx2_f32, torch.float32), _stream()), "pai_conv_dgrad_f32add")
+
+
+def head_loss_ok(d, has_bias: bool = False) -> bool:
+    """``head_loss`` takes this layer (pai_head_loss_ok; host only): the bias-free bf16 k4 s1 p1 C -> 1 PatchGAN head whose
+    image fits the kernel's LDS, unless the tunable ``head_fused`` is 0."""
+    return bool(L.load().pai_head_loss_ok(C.byref(d), int(bool(has_bias))))
+
+
+def head_loss(d, a3, w_fwd, w_dgrad, n_first, target_first, target_rest, loss_scale, loss, grad_scale, logits, dl=None,
+              dl_f32=None, du=None, act=ACT_LRELU):
+    """The PatchGAN head, BCE-with-logits against a per-image constant target (images below ``n_first``: ``target_first``)
+    and, with ``du``, the head's input gradient times act'(a3) in one launch (pai_head_loss)."""
+    L.check(L.load().pai_head_loss(C.byref(d), _p(a3, torch.bfloat16), _p(w_fwd), _p(w_dgrad), int(n_first),
+                                   float(target_first), float(target_rest), float(loss_scale), _p(loss, torch.float64),
+                                   float(grad_scale), _p(logits, torch.float32), _p(dl, torch.bfloat16),
+                                   _p(dl_f32, torch.float32), _p(du, torch.bfloat16), _p(a3) if du is not None else None,
+                                   int(act), _stream()), "pai_head_loss")
+
+
 def conv_dgrad_bn_rows_max(d) -> int:
     return L.load().pai_conv_dgrad_bn_rows_max(C.byref(d))
 
