@@ -68,7 +68,10 @@ const char* pai_last_error(void);
  * 139: train-mode FiLM norm (pai_film_norm_fwd, pai_film_norm_bwd, pai_film_norm_ws_floats, pai_film_norm_slabs); PAI_ACT_SILU
  * is also taken by these.
  * 140: the PatchGAN head with its loss in one launch (pai_head_loss, pai_head_loss_ok); fp32 input gradient with an addend
- * (pai_conv_dgrad_f32add, pai_conv_dgrad_f32add_ok); tunables "head_fused", "head_loss_rg". */
+ * (pai_conv_dgrad_f32add, pai_conv_dgrad_f32add_ok); tunables "head_fused", "head_loss_rg".
+ * 141: ReLU keeps a NaN in the element-wise passes (pai_bn_apply, pai_bn2_add_act, pai_add_act, the one-launch finish of
+ * pai_conv_fwd_bn; they stored 0 for it); pai_bn_apply / pai_bn2_add_act refuse a dtype other than PAI_F32 / PAI_BF16 (they
+ * ran it as bf16). */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -349,13 +352,26 @@ int pai_bn_finalize(const float* stats, int rows, int C, int64_t count, const fl
 int pai_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
                        const float* running_var, float eps, float* scale, float* shift,
                        void* stream);
-/* out = act(z*scale + shift), elementwise over [M][C]. */
+/* out = act(z*scale + shift), elementwise over [M][C] (one fma, then the activation; bf16: rounded once on the store).
+ * dtype PAI_F32 or PAI_BF16, anything else is refused (ABI 141), as is C % 8 != 0.  out may be z itself (every vector is
+ * read before the same thread writes it); partial overlap is not allowed.
+ * NaN (ABI 141): act is applied as aten applies it -- ReLU is clamp_min(v, 0), which KEEPS a NaN (it stored 0 before), and
+ * LeakyReLU always did; -inf under ReLU is 0, +-0 give +0.  So a NaN channel of pai_bn_finalize (one NaN in z makes mean,
+ * rstd, scale, shift and the running statistics of its channel NaN) is a NaN channel of the output, not a dead one.  The
+ * same holds for pai_bn2_add_act (both activations), pai_add_act and the one-launch finish of pai_conv_fwd_bn, like the
+ * convolution epilogues and pai_denormalize before them.  Sites that still differ from aten, on purpose and untouched:
+ * the on-load ReLU of the input prologue (pai_conv_fwd_pro / pai_conv_wgrad_pro and relu1 / relu2 of the descriptor: an
+ * fmaxf in the operand loads of the matrix kernels turns a NaN into 0 -- an extra instruction per element there has a
+ * cost nobody has measured), the fmaxf ReLU of the SIMT convolution and of the attention gate (pai_gate_*), and the
+ * backward sign tests (act'(NaN) = the negative side's slope, so du = 0 under ReLU where aten gives NaN). */
 int pai_bn_apply(int dtype, const void* z, int64_t M, int C, const float* scale,
                  const float* shift, int act, void* out, void* stream);
 /* out = act(act_a(za*scale_a + shift_a) + (zb*scale_b + shift_b)) over [M][C]: BatchNorm (+ its own ReLU: the ResNeXt
  * block) of the residual branch + BatchNorm of the skip branch (scale_b = shift_b = NULL: identity skip, zb added as it is)
  * + sum + activation, the tail of the residual blocks (reference models/res_unet.py:74,105,160-171,
- * models/trans_unet.py:227-236), in one pass. */
+ * models/trans_unet.py:227-236), in one pass.  fp32: the roundings of the three passes it stands for (fma, fma, add).
+ * dtype PAI_F32 or PAI_BF16 only, C % 8 == 0, scale_b and shift_b both or neither (checked).  A NaN in either branch stays
+ * a NaN through act_a and act (ReLU = clamp_min, ABI 141: see pai_bn_apply). */
 int pai_bn2_add_act(int dtype, const void* za, const float* scale_a, const float* shift_a, const void* zb,
                     const float* scale_b, const float* shift_b, int64_t M, int C, int act_a, int act, void* out,
                     void* stream);
@@ -410,7 +426,8 @@ int pai_dropout2d(int dtype, const void* x, const float* mask, int N, int64_t HW
  *                     (first maximum in row-major window order, as aten::max_pool2d_with_indices)
  *   pai_maxpool2_bwd  dx [N][H][W][C] = dout routed to the arg-max, zeros elsewhere
  *   pai_upsample2     out [N][2H][2W][C];  pai_upsample2_bwd  dx [N][H][W][C] = sum of the 2x2 window of dout
- *   pai_add_act       out = act(a + b)   (backward: pai_act_bwd on the stored sum)
+ *   pai_add_act       out = act(a + b)   (backward: pai_act_bwd on the stored sum); a NaN sum stays a NaN under ReLU too
+ *                     (ABI 141: see pai_bn_apply)
  * ------------------------------------------------------------------------- */
 int pai_maxpool2(int dtype, const void* x, int N, int H, int W, int C, void* out, unsigned char* idx, void* stream);
 int pai_maxpool2_bwd(int dtype, const void* dout, const unsigned char* idx, int N, int H, int W, int C, void* dx,

@@ -4,7 +4,10 @@ reference's blocks (models/res_unet.py:133-171, models/pix2pix.py:70,106; aten::
 
 ``pai_set_tunable("ew_stream", 0)`` sends a call to the generic kernel: forward-side passes must agree BIT FOR BIT (same
 operations in the same order), the BatchNorm backward (re-associated: dz = A du + (B (z - mean) + K)) to one bf16 rounding
-of the generic kernel's result (plus the fp32 cancellation error where dz is tiny) and to bf16 rounding of the fp64 formula; the partial sums to fp32 summation error."""
+of the generic kernel's result (plus the fp32 cancellation error where dz is tiny) and to bf16 rounding of the fp64 formula; the partial sums to fp32 summation error.
+
+The sweep kernels are also run with the grid capped at 3 and at 5 blocks (tunable ew_stream_blocks): tens of ragged trips over
+the same tensors must give the bits of the one-trip call, and an in-place pai_bn_apply the bits of the out-of-place one."""
 import pytest
 import torch
 
@@ -232,3 +235,107 @@ def test_block_tail_backward_both_branches_in_one_pass(both, shape, act):
             assert bool(((fa - fb).abs() <= 2 ** -7 * torch.maximum(fa.abs(), fb.abs()) + 4e-6 * (d.abs().float() + 1)).all())
         else:
             assert torch.equal(g_.view(torch.int16), w_.view(torch.int16))
+
+
+# ---- more than one sweep trip ---------------------------------------------------------------------------------------------------
+def _bits(t):
+    return t.view(torch.int16)
+
+
+@pytest.mark.parametrize("blocks", [3, 5])
+@pytest.mark.parametrize("shape", SHAPES, ids=[f"{m}x{c}" for m, c in SHAPES])
+def test_sweeps_of_many_trips_give_the_same_bits(pai, shape, blocks):
+    """The five sweep kernels (bn_apply_stream_k, bn2_add_act_stream_k, add_act_stream_k, bn_bwd_apply_stream_k,
+    bn2_bwd_apply_stream_k) walk the tensor in steps of gridDim.x * 256 * 4 vectors (the two-branch backward: * 2), the grid
+    capped by the tunable ew_stream_blocks (default 16384: a second trip starts at 268 MB of bf16, which the residual U-Net
+    at 512 x 512 passes four times over and no test reaches).  With the cap at 3 and at 5 blocks every SHAPES tensor takes
+    tens of ragged trips: the SAME BITS as the same call at the default grid are required -- the work of an element does not
+    depend on which trip reaches it -- plain and non-temporal, and the forward ones must in turn equal the generic kernels.
+    The two slab reductions (bn_bwd_reduce_stream_k, bn2_bwd_reduce_stream_k) take their grid from the partial-row count, not
+    from this tunable: nothing of theirs changes here and they are left to the tests above."""
+    from thesis_pai_reconstruction_amd import ops
+    M, C = shape
+    dt = torch.bfloat16
+    za, d, mean_a, rstd_a, gamma_a, sa, ha = _data(M, C, 11)
+    zb, _, mean_b, rstd_b, gamma_b, sb, hb = _data(M, C, 12)
+    f32 = dict(dtype=torch.float32, device=dev())
+    sums_a, sums_b = torch.linspace(-3, 3, 2 * C, **f32), torch.linspace(2, -2, 2 * C, **f32)
+    assert M * (C // 8) > 5 * 1024 * 8, "tens of trips"
+
+    def forward():
+        out = {}
+        for act in ACTS:
+            o = torch.full_like(za, 7.0)
+            ops.bn_apply(dt, za, M, C, sa, ha, _act(ops, act), o)
+            out["bn_apply", act] = o
+            o = torch.full_like(za, 7.0)
+            ops.add_act(dt, za, zb, _act(ops, act), o)
+            out["add_act", act] = o
+        for acts in (("relu", "none"), ("none", "relu"), ("relu", "relu"), ("none", "none")):
+            for affb in (False, True):
+                o = torch.full_like(za, 7.0)
+                ops.bn2_add_act(dt, za, sa, ha, zb, sb if affb else None, hb if affb else None, M, C, _act(ops, acts[0]),
+                                _act(ops, acts[1]), o)
+                out["bn2_add_act", acts, affb] = o
+        return out
+
+    def backward():
+        out = {}
+        for act in ACTS:
+            dz = torch.full_like(za, 7.0)
+            if act == "none":
+                ops.bn_bwd_apply(dt, d, za, M, C, mean_a, rstd_a, gamma_a, sums_a, dz)
+            else:
+                ops.bn_bwd_apply_affine(dt, d, _act(ops, act), za, M, C, sa, ha, mean_a, rstd_a, gamma_a, sums_a, dz)
+            out["bn_bwd_apply", act] = dz
+        for act in ("relu", "none"):
+            dza, dzb = torch.full_like(za, 7.0), torch.full_like(za, 7.0)
+            ops.bn2_bwd_apply(dt, d, _act(ops, act), za, zb, M, C, sa, ha, mean_a, rstd_a, gamma_a, sums_a, mean_b, rstd_b, gamma_b,
+                              sums_b, dza, dzb)
+            out["bn2_bwd_apply a", act], out["bn2_bwd_apply b", act] = dza, dzb
+        return out
+
+    try:
+        ops.set_tunable("ew_stream", 0)
+        generic = forward()
+        ops.set_tunable("ew_stream", 1)
+        for nt in (False, True):
+            if nt:
+                ops.set_tunable("ew_stream_nt_mb", 0)
+            ops.set_tunable("ew_stream_blocks")
+            want = {**forward(), **backward()}
+            ops.set_tunable("ew_stream_blocks", blocks)
+            got = {**forward(), **backward()}
+            torch.cuda.synchronize()
+            for k in want:
+                assert torch.equal(_bits(got[k]), _bits(want[k])), (k, nt, blocks, int((_bits(got[k]) != _bits(want[k])).sum()))
+                if k in generic:
+                    assert torch.equal(_bits(got[k]), _bits(generic[k])), (k, nt, "against the generic kernel")
+    finally:
+        for name in ("ew_stream", "ew_stream_nt_mb", "ew_stream_blocks"):
+            ops.set_tunable(name)
+
+
+@pytest.mark.parametrize("blocks", [None, 3], ids=["default_grid", "3_blocks"])
+def test_bn_apply_in_place_streaming(pai, blocks):
+    """out == z (include/pai_hip.h allows exactly this overlap): every vector is read once, before the same thread writes it,
+    in one trip and in many -- the bits of the out-of-place call.  A sweep that visited a vector twice would apply the
+    BatchNorm to its own output."""
+    from thesis_pai_reconstruction_amd import ops
+    M, C = SHAPES[0]
+    z, _, _, _, _, scale, shift = _data(M, C, 13)
+    try:
+        ops.set_tunable("ew_stream", 1)
+        if blocks is not None:
+            ops.set_tunable("ew_stream_blocks", blocks)
+        for nt in (False, True):
+            if nt:
+                ops.set_tunable("ew_stream_nt_mb", 0)
+            want, buf = torch.full_like(z, 7.0), z.clone()
+            ops.bn_apply(torch.bfloat16, z, M, C, scale, shift, ops.ACT_LRELU, want)
+            ops.bn_apply(torch.bfloat16, buf, M, C, scale, shift, ops.ACT_LRELU, buf)
+            torch.cuda.synchronize()
+            assert torch.equal(_bits(buf), _bits(want)), (nt, int((_bits(buf) != _bits(want)).sum()))
+    finally:
+        for name in ("ew_stream", "ew_stream_nt_mb", "ew_stream_blocks"):
+            ops.set_tunable(name)

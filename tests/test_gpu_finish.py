@@ -177,3 +177,49 @@ def test_dgrad_with_producer_batchnorm_backward_fused_finish(pai, case, enc_form
             assert torch.equal(dx2, xg.grad[:, C1:].bfloat16().float()), (name, fused, "dx2")
     for k in range(4):      # dz, dgamma, dbeta, sums: one launch against two, bit for bit
         assert torch.equal(res[1][k], res[0][k]), (name, k)
+
+
+@pytest.mark.parametrize("fused", [1, 0], ids=["one_launch", "two_launches"])
+def test_nan_channel_stays_nan_through_conv_bn_relu(pai, fused):
+    """A NaN bias entry (channel 5) on the smallest case through pai_conv_fwd_bn with ReLU, in the one-launch finish
+    (bn_fin_apply_k) and the two-launch form: z, the statistics, the running statistics and the whole activated column of
+    that channel are NaN -- ReLU keeps a NaN as aten's does, it stored zeros before -- and every other channel has the bits
+    of the run with a clean bias."""
+    case = CASES[0]
+    ops, d = _setup(pai, case)
+    name, tr, N, H, C1, C2, Cout = case
+    dt, bad = torch.bfloat16, 5
+    M = N * (H // 2) ** 2
+    x1, w = _ints((N, C1, H, H), 1), _ints((Cout, C1, 4, 4), 3)
+    gamma, beta = torch.linspace(0.5, 1.5, Cout).to(dev()), torch.linspace(-0.25, 0.25, Cout).to(dev())
+    wm = fwd_pack(w, False)
+    wf = torch.empty(wm.numel(), dtype=dt, device=dev())
+    ops.pack_weights(dt, wm, Cout, 16, C1, wf, None)
+    X1 = nhwc(x1, dt)
+    res = {}
+    ops.set_tunable("bn_fuse_small", fused)
+    try:
+        for nan_bias in (False, True):
+            bias = _ints((Cout,), 7, -3, 3)
+            if nan_bias:
+                bias[bad] = float("nan")
+            stats = torch.zeros(ops.bn_stats_buffer_rows(ops.conv_fwd_stats_rows_max(d)) * 2 * Cout, device=dev())
+            z = torch.empty(M * Cout, dtype=dt, device=dev())
+            a = torch.empty_like(z)
+            rm, rv = torch.zeros(Cout, device=dev()), torch.ones(Cout, device=dev())
+            nbt = torch.zeros((), dtype=torch.int64, device=dev())
+            st = [torch.empty(Cout, device=dev()) for _ in range(4)]
+            ops.conv_fwd_bn(d, X1, None, wf, bias.to(dev()), z, a, ops.ACT_RELU, gamma, beta, 1e-5, 0.1, 1, rm, rv, nbt, st[0], st[1],
+                            st[2], st[3], stats)
+            torch.cuda.synchronize()
+            res[nan_bias] = [z.float().cpu().view(M, Cout), a.float().cpu().view(M, Cout)] + [t.cpu().view(1, Cout) for t in st + [rm, rv]]
+            assert int(nbt) == 1
+    finally:
+        ops.set_tunable("bn_fuse_small")
+    others = [c for c in range(Cout) if c != bad]
+    names = ["z", "a", "mean", "rstd", "scale", "shift", "running_mean", "running_var"]
+    for nm, clean, dirty in zip(names, res[False], res[True]):
+        assert bool(torch.isfinite(clean).all()), nm
+        assert bool(torch.isnan(dirty[:, bad]).all()), (nm, fused, "channel 5 is not NaN everywhere")
+        assert torch.equal(dirty[:, others], clean[:, others]), (nm, fused, "another channel changed")
+    assert bool((res[False][1][:, bad] == 0).any()) and bool((res[False][1][:, bad] > 0).any())      # ReLU does clip this channel

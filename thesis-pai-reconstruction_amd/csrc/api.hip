@@ -14,7 +14,7 @@ void pai_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* pai_last_error(void) { return g_err; }
-extern "C" int pai_version(void) { return 140; }   // 110: handles, tunables, device-side Adam step, *_take, pack multi; 120: weight-gradient workspace; 121: pai_adam_pack, pai_bn_bwd_apply_affine; 130: launch plans; 131: pai_lerp_multi; 132: input prologue (pai_conv_fwd_pro / pai_conv_wgrad_pro); 133: device-resident data set (data.hip); 134: report evaluation (eval.hip); 135: Palette sampling (palette.hip); 136: pai_mha_kernel_name; 137: denormalize keeps NaN, empty tensors in the multi-tensor calls; 138: differentiable spatial attention; 139: train-mode FiLM norm (film_norm.hip); 140: pai_head_loss (head.hip), pai_conv_dgrad_f32add
+extern "C" int pai_version(void) { return 141; }   // 110: handles, tunables, device-side Adam step, *_take, pack multi; 120: weight-gradient workspace; 121: pai_adam_pack, pai_bn_bwd_apply_affine; 130: launch plans; 131: pai_lerp_multi; 132: input prologue (pai_conv_fwd_pro / pai_conv_wgrad_pro); 133: device-resident data set (data.hip); 134: report evaluation (eval.hip); 135: Palette sampling (palette.hip); 136: pai_mha_kernel_name; 137: denormalize keeps NaN, empty tensors in the multi-tensor calls; 138: differentiable spatial attention; 139: train-mode FiLM norm (film_norm.hip); 140: pai_head_loss (head.hip), pai_conv_dgrad_f32add; 141: ReLU keeps a NaN in pai_bn_apply / pai_bn2_add_act / pai_add_act, which refuse unknown dtypes
 
 // build-option bits; none since ABI 130 (bit 0 announced the round-2 experiment kernels, which were removed)
 extern "C" int pai_build_flags(void) { return 0; }

@@ -213,6 +213,7 @@ static int ew_grid(int64_t nvec) {
 extern "C" int pai_bn_apply(int dtype, const void* z, int64_t M, int C, const float* scale,
                             const float* shift, int act, void* out, void* stream) {
     PAI_CHECK(z && out && scale && shift, "pai_bn_apply: null pointer");
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_bn_apply: dtype=%d must be PAI_F32 or PAI_BF16", dtype);
     PAI_CHECK(C % 8 == 0, "pai_bn_apply: C=%d must be a multiple of 8", C);
     const int64_t nvec = M * C / 8;
     hipStream_t s = (hipStream_t)stream;
@@ -261,6 +262,7 @@ extern "C" int pai_bn2_add_act(int dtype, const void* za, const float* scale_a, 
                                const float* scale_b, const float* shift_b, int64_t M, int C, int act_a, int act, void* out,
                                void* stream) {
     PAI_CHECK(za && zb && out && scale_a && shift_a, "pai_bn2_add_act: null pointer");
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_bn2_add_act: dtype=%d must be PAI_F32 or PAI_BF16", dtype);
     PAI_CHECK((scale_b == nullptr) == (shift_b == nullptr), "pai_bn2_add_act: scale_b and shift_b go together");
     PAI_CHECK(C % 8 == 0, "pai_bn2_add_act: C=%d must be a multiple of 8", C);
     for (int t : {act_a, act})

@@ -97,7 +97,7 @@ template <> struct V8<bf16_t> {
 __device__ __forceinline__ float act_apply(float v, int act) {
     switch (act) {
         case PAI_ACT_LRELU: return v > 0.f ? v : 0.2f * v;
-        case PAI_ACT_RELU: return v > 0.f ? v : 0.f;
+        case PAI_ACT_RELU: return !(v <= 0.f) ? v : 0.f;      // a NaN stays a NaN (aten's clamp_min), as in act_fwd
         case PAI_ACT_TANH: return tanhf(v);
         default: return v;
     }

@@ -40,7 +40,7 @@ __device__ __forceinline__ u32x4 pack8(const float* v) {
     return w;
 }
 template <int ACT> __device__ __forceinline__ float actc(float v) {
-    if (ACT == PAI_ACT_RELU) return v > 0.f ? v : 0.f;
+    if (ACT == PAI_ACT_RELU) return !(v <= 0.f) ? v : 0.f;      // a NaN stays a NaN, as act_apply (common.h)
     if (ACT == PAI_ACT_LRELU) return v > 0.f ? v : 0.2f * v;
     return v;
 }
