@@ -71,7 +71,8 @@ const char* pai_last_error(void);
  * (pai_conv_dgrad_f32add, pai_conv_dgrad_f32add_ok); tunables "head_fused", "head_loss_rg".
  * 141: ReLU keeps a NaN in the element-wise passes (pai_bn_apply, pai_bn2_add_act, pai_add_act, the one-launch finish of
  * pai_conv_fwd_bn; they stored 0 for it); pai_bn_apply / pai_bn2_add_act refuse a dtype other than PAI_F32 / PAI_BF16 (they
- * ran it as bf16). */
+ * ran it as bf16); the train-mode Palette U-Net pass (pai_avgpool2_bwd, pai_silu_bwd: additions, the number the library
+ * already reported stays). */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -819,6 +820,12 @@ int pai_data_kernel_name(int op, int src_dtype, char* name, int name_len);
  * coefficients a, b (pai_bn_eval_coeffs) and emb_out (dtype) [N] rows of ld elements: scale = the first C columns of a row,
  * shift = the next C ("use_scale_shift_norm", unet.py:206-210).
  * pai_avgpool2: out [N][H/2][W/2][C] = the 2 x 2 mean of x [N][H][W][C] (AvgPool2d(2), unet.py:98); H, W even, C % 8 == 0.
+ * pai_avgpool2_bwd (ABI 141): the backward of pai_avgpool2; H, W, C are those of dx [N][H][W][C] and dout is [N][H/2][W/2][C]:
+ * dx[n][2i+a][2j+b][c] = 0.25 dout[n][i][j][c] for a, b in {0, 1} (exact in both dtypes).  Every element of dx is written once.
+ * The refusals of the forward (dtype, NULL, even H and W, C % 8 == 0, size) and 16-byte alignment, all before any launch.
+ * pai_silu_bwd (ABI 141): du = g SiLU'(u) on numel elements of dtype, SiLU'(u) = sig(u) (1 + u (1 - sig(u))) with sig and
+ * 1 - sig formed from exp(-|u|) as in pai_film_norm_*: finite at u = +-100, a NaN stays a NaN; fp32 uses expf and a division,
+ * bf16 the hardware exp2 and reciprocal.  Any numel >= 1; tensors 16-byte aligned; du may alias g.
  * pai_gamma_embedding: out (dtype) [N][dim] = [cos(g f_i) | sin(g f_i) | 0 if dim is odd], f_i = exp(-ln(10000) i / (dim / 2))
  * (nn.py:140-157).
  * pai_palette_step: one reverse step on `pixels` pixels of C channels, [pixel][channel].  model_out (dtype) has C columns
@@ -836,6 +843,8 @@ int pai_affine_act(int dtype, const void* x, int64_t rows_per_sample, int N, int
 int pai_film_coeffs(int dtype, int C, int N, const float* a, const float* b, const void* emb_out, int64_t ld, float* A,
                     float* B, void* stream);
 int pai_avgpool2(int dtype, const void* x, int N, int H, int W, int C, void* out, void* stream);
+int pai_avgpool2_bwd(int dtype, const void* dout, int N, int H, int W, int C, void* dx, void* stream);
+int pai_silu_bwd(int dtype, const void* g, const void* u, int64_t numel, void* du, void* stream);
 int pai_gamma_embedding(int dtype, const float* gammas, int N, int dim, void* out, void* stream);
 int pai_palette_step(int dtype, const void* model_out, const float* y_t, const float* noise, int64_t pixels, int C,
                      int learn_var, int add_noise, float s1, float rs, float c0, float c1, float log_lo, float log_hi,

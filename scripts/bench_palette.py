@@ -5,11 +5,16 @@ beside ``torch.nn.functional.scaled_dot_product_attention`` on the same data (bo
 Last the train-mode norm site ``pai_film_norm_fwd`` / ``pai_film_norm_bwd`` (FiLM + SiLU + mask, bf16) at the class-default levels,
 as GB/s of the bytes the passes must move (forward: 2 tensors + the mask; backward: 5 tensors + 2 masks), beside torch's own
 ``batch_norm`` + FiLM + ``silu`` + mask forward and autograd on the same shapes (NCHW, torch's layout) and charged the same bytes.
+``--train`` adds the row ``unet_train``: ms per ``UNet.forward_train`` + backward at the class defaults (dropout 0.1, masks drawn
+per pass) at ``--train-batch`` images (default 4: the pass keeps every block's input, norm input and mask for the backward), with
+``--count-launches`` also the kernel launches of one such pass as the profiler sees them; and ``avgpool2_bwd`` alone as GB/s
+of the bytes it must move (read dout, write dx), the figure to put beside scripts/bench_hbm.py's rate.
 Random normal data throughout (never zeros: MI355X_MICROARCH, data-dependent power).  One JSON line per measurement.
 
     python scripts/bench_palette.py [--precision bf16-mixed] [--batch 8] [--size 256] [--steps 100] [--mults 1,1,2,2,4,4]
                                     [--attention-res 16,8] [--no-sampler] [--no-attention] [--forward-only K]
-                                    [--no-film-norm] [--film-norm-only]
+                                    [--no-film-norm] [--film-norm-only] [--train] [--train-only] [--train-batch 4]
+                                    [--count-launches]
 
 ``--forward-only K`` runs K U-Net forward passes and nothing else (the run to put under a kernel trace); ``--film-norm-only``
 runs the film_norm rows and nothing else (no model is built).
@@ -132,6 +137,58 @@ def bench_film_norm(dtype, n):
         print(json.dumps(row), flush=True)
 
 
+AVGPOOL_SHAPES = [(256, 128), (128, 128), (64, 256), (32, 256), (16, 512)]     # (H = W of dx, C): the class defaults at 256 x 256
+
+
+def bench_avgpool_bwd(dtype, n):
+    es = torch.empty(0, dtype=dtype).element_size()
+    for side, C in AVGPOOL_SHAPES:
+        dout = torch.randn(n, side // 2, side // 2, C, device="cuda").to(dtype)
+        dx = torch.empty(n, side, side, C, dtype=dtype, device="cuda")
+        ms = timed(lambda: ops.avgpool2_bwd(dtype, dout, n, side, side, C, dx), 3, 100)
+        print(json.dumps({"bench": "avgpool2_bwd", "dtype": str(dtype), "N": n, "H": side, "W": side, "C": C, "ms": round(ms, 4),
+                          "GBps": round((dout.numel() + dx.numel()) * es / ms / 1e6, 1)}), flush=True)
+
+
+def bench_train(a, mults, att):
+    """ms per forward_train + backward at the class defaults (dropout 0.1); optionally the launches of one pass."""
+    dev = torch.device("cuda:0")
+    model = pai.Palette(1, 1, mults, att, 0.1, "linear", False)
+    with torch.no_grad():
+        for k, v in model.unet.state_dict().items():
+            if k.endswith("running_var"):
+                v.uniform_(1.0, 1.2)
+            elif v.dim() > 1:
+                v.normal_(0.0, 0.02)
+    model.to(dev)
+    model.train()
+    model.set_precision(a.precision)
+    n = a.train_batch
+    x, y = torch.randn(n, 1, a.size, a.size, device=dev), torch.randn(n, 1, a.size, a.size, device=dev)
+    g = torch.rand(n, device=dev)
+    dout = torch.randn(n, 1, a.size, a.size, device=dev)
+
+    def step():
+        for p in model.unet.parameters():
+            p.grad = None
+        model.unet.forward_train(x, y, g).backward(dout)
+
+    ms = timed(step, 2, 5)
+    row = {"bench": "unet_train", "precision": a.precision, "N": n, "size": a.size, "mults": mults, "attention_res": att,
+           "dropout": 0.1, "ms": round(ms, 3), "tflops": round(6 * n * model.unet.macs(a.size, a.size) / ms / 1e9, 2),
+           "peak_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2), "launches": None}
+    if a.count_launches:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            step()
+            torch.cuda.synchronize()
+        kernels = [e for e in prof.events() if str(e.device_type).endswith("CUDA") and "Memcpy" not in e.name
+                   and "Memset" not in e.name]
+        row["launches"] = len(kernels)
+        row["library_launches"] = sum(1 for e in kernels if not e.name.startswith("void at::") and "at::native" not in e.name)
+    print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="bf16-mixed")
@@ -145,7 +202,16 @@ def main():
     ap.add_argument("--forward-only", type=int, default=0)
     ap.add_argument("--no-film-norm", action="store_true")
     ap.add_argument("--film-norm-only", action="store_true")
+    ap.add_argument("--train", action="store_true")
+    ap.add_argument("--train-only", action="store_true")
+    ap.add_argument("--train-batch", type=int, default=4)
+    ap.add_argument("--count-launches", action="store_true")
     a = ap.parse_args()
+    if a.train_only:
+        torch.manual_seed(0)
+        bench_train(a, tuple(int(v) for v in a.mults.split(",")), tuple(int(v) for v in a.attention_res.split(",")))
+        bench_avgpool_bwd(torch.bfloat16, a.batch)
+        return
     if a.film_norm_only:
         torch.manual_seed(0)
         bench_film_norm(torch.bfloat16, a.batch)
@@ -183,6 +249,10 @@ def main():
         bench_attention(dtype, a.batch, 4)
     if not a.no_film_norm:
         bench_film_norm(torch.bfloat16, a.batch)
+    if a.train:
+        del model
+        bench_train(a, mults, att)
+        bench_avgpool_bwd(torch.bfloat16, a.batch)
 
 
 if __name__ == "__main__":

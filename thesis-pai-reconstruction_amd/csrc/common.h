@@ -64,6 +64,18 @@ template <> struct Conv<bf16_t> {
     static __device__ __forceinline__ void st(bf16_t* p, float v) { *p = f2bf(v); }
 };
 
+// ---- sigmoid pair (film_norm.hip, pai_silu_bwd) ------------------------------------------
+// sigmoid(u) and 1 - sigmoid(u) from e = exp(-|u|) in (0, 1]: no overflow at u = -100, no cancellation in 1 - sig at large
+// u, and a NaN stays a NaN (every comparison with it is false and both branches carry it).
+template <bool EXACT> __device__ __forceinline__ void fn_sig(float u, float& sig, float& oms) {
+    const float e = EXACT ? expf(-fabsf(u)) : __expf(-fabsf(u));
+    const float r = EXACT ? 1.0f / (1.0f + e) : __builtin_amdgcn_rcpf(1.0f + e);
+    const float er = e * r;
+    const bool pos = u >= 0.f;
+    sig = pos ? r : er;
+    oms = pos ? er : r;
+}
+
 // ---- 8-wide vector access ----------------------------------------------------------------
 template <typename T> struct V8;
 template <> struct V8<float> {

@@ -24,16 +24,7 @@ constexpr int FV = 4;                  // vectors in flight per thread and tenso
 constexpr int FN_SLAB_ROWS = 64;       // rows of a slab until FN_MAX_SLABS is reached
 constexpr int FN_MAX_SLABS = 256;
 
-// sigmoid(u) and 1 - sigmoid(u) from e = exp(-|u|) in (0, 1]: no overflow at u = -100, no cancellation in 1 - sig at large
-// u, and a NaN stays a NaN (every comparison with it is false and both branches carry it).
-template <bool EXACT> __device__ __forceinline__ void fn_sig(float u, float& sig, float& oms) {
-    const float e = EXACT ? expf(-fabsf(u)) : __expf(-fabsf(u));
-    const float r = EXACT ? 1.0f / (1.0f + e) : __builtin_amdgcn_rcpf(1.0f + e);
-    const float er = e * r;
-    const bool pos = u >= 0.f;
-    sig = pos ? r : er;
-    oms = pos ? er : r;
-}
+// fn_sig (common.h): sigmoid(u) and 1 - sigmoid(u) from e = exp(-|u|).
 template <int ACT, bool EXACT> __device__ __forceinline__ float fn_act(float u) {
     if (ACT != PAI_ACT_SILU) return u;
     float sig, oms;

@@ -19,6 +19,8 @@
 //                        site of the network, FiLM included.
 //   pai_film_coeffs      A = a (1 + scale), B = b (1 + scale) + shift from the BatchNorm eval coefficients and emb_out.
 //   pai_avgpool2         2 x 2 mean (Downsample(use_conv=False)).
+//   pai_avgpool2_bwd     its backward: dout / 4 to the four positions (training).
+//   pai_silu_bwd         du = g SiLU'(u): the two SiLUs of the embedding path (training).
 //   pai_gamma_embedding  [cos(g f_i) | sin(g f_i)] (nn.py:140-157).
 //   pai_palette_step     one reverse diffusion step, elementwise (palette.py:233-306).
 #include "common.h"
@@ -900,6 +902,97 @@ extern "C" int pai_avgpool2(int dtype, const void* x, int N, int H, int W, int C
         hipLaunchKernelGGL(avgpool2_k<float>, grid, dim3(256), 0, s, (const float*)x, nvec, H / 2, W / 2, C / 8, (float*)out);
     else
         hipLaunchKernelGGL(avgpool2_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, nvec, H / 2, W / 2, C / 8, (bf16_t*)out);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- backward of the 2 x 2 mean --------------------------------------------------------------------------------------------------------
+// The geometry of avgpool2_k: a thread owns one 16-byte channel vector of dout and stores it, times 0.25, to the four
+// positions of dx it was averaged from.  Every element of dx is written exactly once.
+template <typename T>
+__global__ __launch_bounds__(256) void avgpool2_bwd_k(const T* dout, int64_t nvec, int OH, int OW, int G, T* dx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvec) return;
+    const int cg = (int)(i % G);
+    int64_t p = i / G;
+    const int ox = (int)(p % OW);
+    p /= OW;
+    const int oy = (int)(p % OH);
+    const int64_t n = p / OH;
+    const int C = G * 8, W = 2 * OW;
+    float v[8];
+    V8<T>::ld(dout + i * 8, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] *= 0.25f;
+    T* d = dx + (((n * 2 * OH + 2 * oy) * W + 2 * ox) * (int64_t)C) + cg * 8;
+    V8<T>::st(d, v);
+    V8<T>::st(d + C, v);
+    V8<T>::st(d + (int64_t)W * C, v);
+    V8<T>::st(d + (int64_t)W * C + C, v);
+}
+
+extern "C" int pai_avgpool2_bwd(int dtype, const void* dout, int N, int H, int W, int C, void* dx, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_avgpool2_bwd: dtype=%d", dtype);
+    PAI_CHECK(dout && dx, "pai_avgpool2_bwd: null tensor");
+    PAI_CHECK(((uintptr_t)dout & 15) == 0 && ((uintptr_t)dx & 15) == 0, "pai_avgpool2_bwd: tensors must be 16-byte aligned");
+    PAI_CHECK(N >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "pai_avgpool2_bwd: N=%d H=%d W=%d (even sizes)", N, H, W);
+    PAI_CHECK(C >= 8 && C % 8 == 0, "pai_avgpool2_bwd: C=%d (a multiple of 8)", C);
+    const int64_t nvec = (int64_t)N * (H / 2) * (W / 2) * (C / 8);
+    PAI_CHECK((nvec + 255) / 256 < (1ll << 31), "pai_avgpool2_bwd: tensor too large");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((nvec + 255) / 256));
+    if (dtype == PAI_F32)
+        hipLaunchKernelGGL(avgpool2_bwd_k<float>, grid, dim3(256), 0, s, (const float*)dout, nvec, H / 2, W / 2, C / 8, (float*)dx);
+    else
+        hipLaunchKernelGGL(avgpool2_bwd_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)dout, nvec, H / 2, W / 2, C / 8, (bf16_t*)dx);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- du = g SiLU'(u) -------------------------------------------------------------------------------------------------------------------
+// SiLU'(u) = sig (1 + u (1 - sig)) with sig and 1 - sig from fn_sig, as film_norm.hip forms it.  A thread owns eight
+// consecutive elements: one 16-byte vector per tensor where all eight exist, element by element in the ragged tail.  It
+// reads its elements of g before it writes them to du, so du may alias g.
+template <typename T>
+__global__ __launch_bounds__(256) void silu_bwd_k(const T* g, const T* u, int64_t numel, T* du) {
+    const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (i0 >= numel) return;
+    constexpr bool EXACT = sizeof(T) == 4;
+    if (i0 + 8 <= numel) {
+        float gv[8], uv[8];
+        V8<T>::ld(g + i0, gv);
+        V8<T>::ld(u + i0, uv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float sig, oms;
+            fn_sig<EXACT>(uv[e], sig, oms);
+            gv[e] *= sig * fmaf(uv[e], oms, 1.f);
+        }
+        V8<T>::st(du + i0, gv);
+    } else {
+        for (int64_t i = i0; i < numel; ++i) {
+            const float uu = Conv<T>::ld(u + i);
+            float sig, oms;
+            fn_sig<EXACT>(uu, sig, oms);
+            Conv<T>::st(du + i, Conv<T>::ld(g + i) * (sig * fmaf(uu, oms, 1.f)));
+        }
+    }
+}
+
+extern "C" int pai_silu_bwd(int dtype, const void* g, const void* u, int64_t numel, void* du, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_silu_bwd: dtype=%d", dtype);
+    PAI_CHECK(g && u && du, "pai_silu_bwd: null tensor");
+    PAI_CHECK(((uintptr_t)g & 15) == 0 && ((uintptr_t)u & 15) == 0 && ((uintptr_t)du & 15) == 0,
+              "pai_silu_bwd: tensors must be 16-byte aligned");
+    PAI_CHECK(numel >= 1, "pai_silu_bwd: numel=%lld", (long long)numel);
+    const int64_t nthr = (numel + 7) / 8;
+    PAI_CHECK((nthr + 255) / 256 < (1ll << 31), "pai_silu_bwd: tensor too large");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((nthr + 255) / 256));
+    if (dtype == PAI_F32)
+        hipLaunchKernelGGL(silu_bwd_k<float>, grid, dim3(256), 0, s, (const float*)g, (const float*)u, numel, (float*)du);
+    else
+        hipLaunchKernelGGL(silu_bwd_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)g, (const bf16_t*)u, numel, (bf16_t*)du);
     PAI_LAUNCH_CHECK();
     return 0;
 }

@@ -649,7 +649,8 @@ def spatial_attention(qkv, heads: int):
 # --------------------------------------------------------------------------------------
 class _FilmNormAct(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, emb_out, mask, keep_scale, act, running_mean, running_var, nbt, momentum, eps):
+    def forward(ctx, x, weight, bias, emb_out, mask, keep_scale, act, running_mean, running_var, nbt, momentum, eps,
+                advance_in_backward=False):
         n, c = x.shape[0], x.shape[-1]
         rows = x[0].numel() // c
         m, dtype = n * rows, x.dtype
@@ -667,18 +668,29 @@ class _FilmNormAct(torch.autograd.Function):
         ld = emb_out.shape[1] if emb_out is not None else 0
         out = torch.empty_like(x)
         ops.film_norm_fwd(dtype, x, rows, n, c, mean, rstd, gamma, beta, emb_out, ld, mask, keep_scale, act, out)
-        ctx.save_for_backward(x, mean, rstd, gamma, beta, emb_out, mask)
+        # advance_in_backward: the reference runs this norm's forward a second time while it differentiates (its AttentionBlock
+        # is always under gradient checkpointing), so the running buffers advance once more, on the same batch statistics, in
+        # the backward pass.  The statistics are kept for that; nothing is recomputed.
+        ctx.again = None
+        if advance_in_backward and running_mean is not None:
+            ctx.again = (running_mean, running_var, nbt, srows, m, momentum, eps)
+        ctx.save_for_backward(x, mean, rstd, gamma, beta, emb_out, mask, stats if ctx.again else None)
         ctx.dims = (n, rows, c, ld, keep_scale, act)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        x, mean, rstd, gamma, beta, emb_out, mask = ctx.saved_tensors
+        x, mean, rstd, gamma, beta, emb_out, mask, stats = ctx.saved_tensors
         n, rows, c, ld, keep_scale, act = ctx.dims
         if g.dtype != x.dtype:
             raise ops.PaiError(f"film_norm_act: gradient of {g.dtype} for an output of {x.dtype}")
         f32 = dict(dtype=torch.float32, device=x.device)
+        if ctx.again is not None:
+            running_mean, running_var, nbt, srows, m, momentum, eps = ctx.again
+            unused = torch.empty(4, c, **f32)
+            ops.bn_finalize(stats, srows, c, m, gamma, beta, eps, momentum, 1, running_mean, running_var, nbt, unused[0], unused[1],
+                            unused[2], unused[3])
         dx = torch.empty_like(x)
         # the columns of demb past 2 C belong to nobody: zero, as the gradient of columns the op does not read
         demb = torch.zeros_like(emb_out) if emb_out is not None else None
@@ -686,17 +698,19 @@ class _FilmNormAct(torch.autograd.Function):
         ws = torch.empty(ops.film_norm_ws_floats(n, rows, c), **f32)
         ops.film_norm_bwd(x.dtype, g.contiguous(), x, rows, n, c, mean, rstd, gamma, beta, emb_out, ld, mask, keep_scale, act, dx,
                           demb, dgb[:c], dgb[c:], ws)
-        return (dx, dgb[:c], dgb[c:], demb) + (None,) * 8
+        return (dx, dgb[:c], dgb[c:], demb) + (None,) * 9
 
 
 def film_norm_act(x, weight, bias, emb_out=None, *, act="silu", dropout_mask=None, p=0.0, running_mean=None, running_var=None,
-                  num_batches_tracked=None, momentum=0.1, eps=1e-5):
+                  num_batches_tracked=None, momentum=0.1, eps=1e-5, advance_in_backward=False):
     """A norm site of the guided-diffusion U-Net in training (reference models/guided_diffusion/unet.py:141-172,206-210):
     ``Dropout(act(BatchNorm(x) * (1 + scale) + shift))`` on batch statistics, with a backward.  x: [N, rows, C] or NHWC
     [N, H, W, C] (fp32 or bf16, contiguous, on the device); weight, bias: fp32 [C]; emb_out: None or [N, >= 2 C] of x's dtype with
     ``scale | shift`` in its first 2 C columns, contiguous (the output of ``emb_layers``); act: "silu" or "none";
     dropout_mask: uint8 of x's shape, 0 drops; with p > 0 and no mask one is drawn with ``torch.rand`` on the current stream.
-    running_mean / running_var / num_batches_tracked are updated in place as nn.BatchNorm does when they are given.  The
+    running_mean / running_var / num_batches_tracked are updated in place as nn.BatchNorm does when they are given; with
+    ``advance_in_backward`` they advance a second time, on the same batch statistics, when the backward pass runs (the
+    reference's AttentionBlock norm, whose forward runs again under gradient checkpointing).  The
     forward keeps x, mean, rstd, emb_out and the mask, not its output; the backward returns the gradients of x, weight, bias
     and emb_out (``pai_film_norm_fwd`` / ``pai_film_norm_bwd``).  No host synchronisation."""
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
@@ -727,4 +741,5 @@ def film_norm_act(x, weight, bias, emb_out=None, *, act="silu", dropout_mask=Non
         raise ops.PaiError("film_norm_act: dropout_mask must be a contiguous uint8 tensor of x's shape")
     keep_scale = 1.0 / (1.0 - p) if dropout_mask is not None else 1.0
     return _FilmNormAct.apply(x, weight, bias, emb_out, dropout_mask, keep_scale, ops.ACT_SILU if act == "silu" else ops.ACT_NONE,
-                              running_mean, running_var, num_batches_tracked, float(momentum), float(eps))
+                              running_mean, running_var, num_batches_tracked, float(momentum), float(eps),
+                              bool(advance_in_backward))

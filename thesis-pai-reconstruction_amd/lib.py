@@ -195,6 +195,8 @@ SIGNATURES = {
     "pai_affine_act": (_I, [_I, _P, _L, _I, _I, _P, _P, _I, _I, _P, _P]),
     "pai_film_coeffs": (_I, [_I, _I, _I, _P, _P, _P, _L, _P, _P, _P]),
     "pai_avgpool2": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
+    "pai_avgpool2_bwd": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
+    "pai_silu_bwd": (_I, [_I, _P, _P, _L, _P, _P]),
     "pai_gamma_embedding": (_I, [_I, _P, _I, _I, _P, _P]),
     "pai_palette_step": (_I, [_I, _P, _P, _P, _L, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "pai_film_norm_slabs": (_I, [_L]),

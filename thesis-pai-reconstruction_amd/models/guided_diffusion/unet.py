@@ -1,5 +1,5 @@
-"""Guided-diffusion U-Net of Palette (reference models/guided_diffusion/unet.py:342-573, nn.py) on the MI355X kernels:
-eval-mode forward only (sampling).
+"""Guided-diffusion U-Net of Palette (reference models/guided_diffusion/unet.py:342-573, nn.py) on the MI355X kernels: the
+eval-mode forward (sampling) and ``forward_train``, the differentiable train-mode pass.
 
 Same module tree as the reference -- ``cond_embed``, ``input_blocks`` / ``middle_block`` / ``output_blocks`` of
 ``EmbedSequential`` holding ``ResBlock`` / ``AttentionBlock``, ``out`` -- built from stock ``nn`` modules as parameter
@@ -15,10 +15,18 @@ call, and the ``emb_layers`` of all blocks are one GEMM over their concatenated 
 
 Weight packs, folded BatchNorm coefficients and that concatenation are cached per (dtype, weight generation): a sampling
 loop of 100 calls builds them once.
+
+``forward_train`` composes the same module tree from autograd Functions (the blocks' ``run_train`` beside ``run``): every
+norm site is ``functional.film_norm_act`` on batch statistics, every convolution ``nnops.ConvBNAct`` without a norm,
+attention ``functional.spatial_attention``.  It caches nothing and drops the eval caches, because the running statistics it
+advances do not move the buffers' version counters.  ``__call__`` / ``run`` in training mode keep raising.
 """
+import weakref
+
 import torch
 import torch.nn as nn
 
+from ... import functional as PF
 from ... import nnops, ops
 from ...ops import ACT_NONE, ACT_SILU, PaiError
 
@@ -43,6 +51,19 @@ class EmbedSequential(nn.Sequential):
         ctx.keep(name, h)
         return h
 
+    def run_train(self, h, h2, ctx, name):
+        for j, layer in enumerate(self):
+            if isinstance(layer, ResBlock):
+                h, h2 = layer.run_train(h, h2, ctx, f"{name}.{j}"), None
+            elif isinstance(layer, AttentionBlock):
+                h = layer.run_train(h, ctx)
+            else:
+                h = ctx.conv(layer, h, h2)
+                h2 = None
+            ctx.keep(f"{name}.{j}", h)
+        ctx.keep(name, h)
+        return h
+
 
 class Upsample(nn.Module):
     """Nearest 2x (the ``use_conv=False`` form is all ``resblock_updown`` uses)."""
@@ -56,6 +77,8 @@ class Upsample(nn.Module):
     def run(self, x, ctx):
         x = ctx.upsample(x)
         return ctx.conv(self.conv, x) if self.use_conv else x
+
+    run_train = run
 
 
 class Downsample(nn.Module):
@@ -75,6 +98,8 @@ class Downsample(nn.Module):
         if self.use_conv:
             raise PaiError("Downsample(use_conv=True) is not built on the HIP path (Palette uses resblock_updown)")
         return ctx.avgpool(x)
+
+    run_train = run
 
 
 class ResBlock(nn.Module):
@@ -131,6 +156,30 @@ class ResBlock(nn.Module):
             s = ctx.conv(self.skip_connection, x, x2)
         return ctx.add(s, h)
 
+    def run_train(self, x, x2, ctx, prefix):
+        """``run`` in training: x (and x2) NHWC -> NHWC, every op an autograd Function.  The norm over cat([x, x2]) is two calls
+        on the two tensors with the two halves of the BatchNorm: it is per channel."""
+        bn = self.in_layers[0]
+        x, xs = nnops.Fork.apply(x)                      # the residual branch and the skip path
+        if x2 is None:
+            h, h2, xs2 = ctx.norm(bn, x), None, None
+        else:
+            c1 = x.shape[3]
+            x2, xs2 = nnops.Fork.apply(x2)
+            h, h2 = ctx.norm(bn, x, lo=0, hi=c1), ctx.norm(bn, x2, lo=c1, hi=self.channels, count=False)
+        if self.updown:
+            if x2 is not None:
+                raise PaiError("ResBlock: a resampling block takes one input tensor")
+            h, xs = self.h_upd.run_train(h, ctx), self.x_upd.run_train(xs, ctx)
+        h = ctx.conv(self.in_layers[2], h, h2)
+        h = ctx.norm(self.out_layers[0], h, emb=ctx.emb[id(self)], p=self.dropout, mask=ctx.masks.get(prefix))
+        h = ctx.conv(self.out_layers[3], h)
+        if isinstance(self.skip_connection, nn.Identity):
+            s = xs if xs2 is None else torch.cat([xs, xs2], dim=3)       # data movement only
+        else:
+            s = ctx.conv(self.skip_connection, xs, xs2)
+        return ctx.add(s, h)
+
 
 class AttentionBlock(nn.Module):
     """norm -> 1x1 qkv -> attention over the H * W positions -> 1x1 proj_out, + x (reference unet.py:217-262 with
@@ -158,6 +207,14 @@ class AttentionBlock(nn.Module):
         att = torch.empty_like(x)
         ops.sattn_fwd(ctx.dtype, qkv, n, hh * ww, self.num_heads, c // self.num_heads, att)
         return ctx.add(x, ctx.conv(self.proj_out, att))
+
+    def run_train(self, x, ctx):
+        """``run`` in training.  The reference block is always under gradient checkpointing, so its norm's forward runs again
+        while it differentiates and the running statistics advance twice per step: ``twice`` moves them again in the backward
+        pass (the statistics are kept; nothing is recomputed)."""
+        x, xs = nnops.Fork.apply(x)
+        qkv = ctx.conv(self.qkv, ctx.norm(self.norm, x, act="none", twice=True))
+        return ctx.add(xs, ctx.conv(self.proj_out, PF.spatial_attention(qkv, self.num_heads)))
 
 
 class _Run:
@@ -228,6 +285,47 @@ class _Run:
         return out
 
 
+class _TrainRun:
+    """One training pass: the autograd Functions behind the blocks' ``run_train`` methods.  ``emb``: id(ResBlock) -> its
+    [N, 2 C] ``scale | shift`` in the storage dtype; ``masks``: ResBlock prefix -> uint8 NHWC dropout mask."""
+
+    def __init__(self, dtype, emb, masks, capture):
+        self.dtype, self.emb, self.masks, self.capture = dtype, emb, masks, capture
+
+    keep = _Run.keep
+
+    def norm(self, bn, x, emb=None, act="silu", p=0.0, mask=None, lo=None, hi=None, count=True, twice=False):
+        """A norm site on the channels [lo, hi) of ``bn`` (all of them by default); ``count``: this call advances
+        ``num_batches_tracked`` (one of the two calls of a norm over a concatenation does)."""
+        w, b, mean, var = bn.weight, bn.bias, bn.running_mean, bn.running_var
+        if lo is not None:
+            w, b, mean, var = w[lo:hi], b[lo:hi], mean[lo:hi], var[lo:hi]
+        return PF.film_norm_act(x, w, b, emb, act=act, dropout_mask=mask, p=float(p), running_mean=mean, running_var=var,
+                                num_batches_tracked=bn.num_batches_tracked if count else None,
+                                momentum=0.1 if bn.momentum is None else bn.momentum, eps=bn.eps, advance_in_backward=twice)
+
+    def conv(self, m, x, x2=None):
+        w = m.weight
+        if w.dim() == 3:                                  # Conv1d over the positions: a 1 x 1 convolution
+            w = w.view(w.shape[0], w.shape[1], 1, 1)
+        c2 = 0 if x2 is None else x2.shape[3]
+        if x.shape[3] + c2 != w.shape[1]:
+            raise PaiError(f"convolution built for {w.shape[1]} input channels, got {x.shape[3]} + {c2}")
+        return nnops.ConvBNAct.apply(x, x2, w, m.bias, None, None, None, True, 1, ACT_NONE, 1, self.dtype, False)
+
+    def upsample(self, x):
+        return nnops.Upsample2.apply(x)
+
+    def avgpool(self, x):
+        if x.shape[1] % 2 or x.shape[2] % 2:
+            raise PaiError(f"UNet: a {x.shape[1]} x {x.shape[2]} level cannot be halved (the input size must divide by "
+                           f"2 ** (levels - 1))")
+        return nnops.AvgPool2.apply(x)
+
+    def add(self, a, b):
+        return nnops.AddAct.apply(a, b, ACT_NONE)
+
+
 class UNet(nn.Module):
     """The U-Net with attention and noise-level embedding (reference unet.py:342-573).
 
@@ -249,6 +347,7 @@ class UNet(nn.Module):
         self.compute_dtype = torch.float32
         self.debug_capture = None        # tests: dict name -> detached fp32 NCHW activation
         self._cache = None
+        self._train_consts = None        # (ones, zeros) fp32 [emb_dim]: the unit coefficients of the embedding path's SiLU
 
         emb_dim = inner_channel * 4
         self.cond_embed = nn.Sequential(nn.Linear(inner_channel, emb_dim), SiLU(), nn.Linear(emb_dim, emb_dim))
@@ -383,6 +482,68 @@ class UNet(nn.Module):
             h = blk.run(h, hs.pop(), ctx, f"output_blocks.{i}")
         a, b = ctx.bn(self.out[0])
         return ctx.conv(self.out[2], ctx.affine(h, a, b, ACT_SILU))
+
+    # ---- training ------------------------------------------------------------------------------------------------------
+    def _embed_train(self, gammas, dtype):
+        """``_embed`` with a tape: id(ResBlock) -> [N, 2 * out_channel] in the storage dtype.  fp32 up to the cast; the
+        ``emb_layers`` of all blocks are one GEMM over the concatenated parameters (``torch.cat`` carries their gradients)."""
+        n, dim = gammas.shape[0], self.inner_channel * 4
+        f32 = dict(dtype=torch.float32, device=gammas.device)
+        e = torch.empty(n, self.inner_channel, **f32)
+        ops.gamma_embedding(gammas, n, self.inner_channel, e)
+        k = self._train_consts
+        if k is None or k[0].device != gammas.device:
+            k = self._train_consts = (torch.ones(dim, **f32), torch.zeros(dim, **f32))
+        for lin in (self.cond_embed[0], self.cond_embed[2]):
+            e = nnops.SiLU.apply(nnops.Linear.apply(e, lin.weight, lin.bias), *k)
+        blocks = [m for m in self.modules() if isinstance(m, ResBlock)]
+        w = torch.cat([b.emb_layers[1].weight for b in blocks], 0)
+        bias = torch.cat([b.emb_layers[1].bias for b in blocks], 0)
+        emb_all = nnops.ToStorage.apply(nnops.Linear.apply(e, w, bias), dtype)
+        parts = nnops.SplitCols.apply(emb_all, tuple(2 * b.out_channel for b in blocks))
+        return {id(b): t for b, t in zip(blocks, parts)}
+
+    def forward_train(self, x, y, gammas, dropout_masks=None):
+        """The train-mode pass: x, y fp32 [N x C x H x W] (read as cat([x, y])) and gammas fp32 [N] on the device ->
+        fp32 [N x out_channel x H x W], connected by autograd to every parameter (not to the inputs).  Every BatchNorm
+        normalises with batch statistics and advances its running buffers as the reference does in one forward + backward:
+        once in the forward, the AttentionBlock norms once more in the backward.  ``dropout_masks``: optional dict from a
+        ResBlock's prefix below this module (``"input_blocks.1.0"``) to a uint8 NHWC mask of its ``out_layers`` dropout (0
+        drops); a block without an entry draws its own when ``dropout`` > 0.  No host synchronisation."""
+        if not self.training:
+            raise PaiError("UNet.forward_train is the training pass: call train() first (eval mode samples through forward)")
+        if not (x.is_cuda and y.is_cuda and gammas.is_cuda):
+            raise PaiError("UNet (HIP) needs HIP device tensors; there is no CPU path")
+        if x.dim() != 4 or x.shape != y.shape or 2 * x.shape[1] != self.in_channel:
+            raise PaiError(f"UNet.forward_train takes x and y of one [N, {self.in_channel // 2}, H, W] shape")
+        dtype = self.compute_dtype
+        # the running statistics advance through raw pointers: their version counters do not move, so the eval coefficients
+        # cached by prepared() would go stale -- dropped now, and again when the backward pass starts (it advances the
+        # attention norms once more)
+        self._cache = None
+        ref = weakref.ref(self)
+
+        def invalidate(_grad):
+            me = ref()
+            if me is not None:
+                me._cache = None
+
+        g = gammas.reshape(-1).float().contiguous()
+        if g.shape[0] != x.shape[0]:
+            raise PaiError(f"UNet.forward_train: {g.shape[0]} gammas for a batch of {x.shape[0]}")
+        ctx = _TrainRun(dtype, self._embed_train(g, dtype), dict(dropout_masks or {}), self.debug_capture)
+        h, hs = nnops.to_nhwc(torch.cat([x, y], dim=1), dtype), []
+        for i, blk in enumerate(self.input_blocks):
+            h = blk.run_train(h, None, ctx, f"input_blocks.{i}")
+            h, skip = nnops.Fork.apply(h)                # the next block and the decoder
+            hs.append(skip)
+        h = self.middle_block.run_train(h, None, ctx, "middle_block")
+        for i, blk in enumerate(self.output_blocks):
+            h = blk.run_train(h, hs.pop(), ctx, f"output_blocks.{i}")
+        out = nnops.FromStorage.apply(ctx.conv(self.out[2], ctx.norm(self.out[0], h)))
+        out.register_hook(invalidate)
+        n, hh, ww, co = out.shape
+        return out.reshape(n, 1, hh, ww) if co == 1 else out.permute(0, 3, 1, 2)
 
     def macs(self, height: int, width: int) -> int:
         """Multiply-accumulates of one forward pass on one ``height`` x ``width`` image: every convolution at the

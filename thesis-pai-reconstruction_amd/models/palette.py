@@ -3,7 +3,8 @@
 Same module tree and state-dict keys as the reference (``unet.*``, ``diffusion.{alphas,gammas,gammas_prev}``,
 ``diffusion_inf.*``), so a checkpoint trained by the reference loads.  Built here: ``forward`` (the reverse process of
 ``diffusion_inf``: one eval-mode U-Net call and one ``pai_palette_step`` launch per step) and ``validation_step``.
-Training (``training_step``, the VLB term, the LinearLR schedule and every backward pass) is not built.
+Training (``training_step``, the VLB term, the LinearLR schedule, the optimizer loop) is not built; the differentiable
+train-mode pass of the U-Net alone is ``unet.forward_train``.
 
 The sample chain stays fp32 in both precisions, as NHWC pixels; the U-Net reads ``[x | y_t]`` in the storage dtype from
 one tensor whose y half the step kernel rewrites.  The six scalars of each step come from a table built once on the

@@ -169,7 +169,9 @@ class _WgradStream:
         again = any(id(p) in self.seen for p in live)
         self.seen.update(id(p) for p in live)
         idx = device.index if device.index is not None else torch.cuda.current_device()
-        if again or any(p.grad is not None or self._hooked(p) for p in live):
+        # (a weight that is no leaf -- a view or a concatenation of parameters -- hands its gradient to further nodes of this
+        # backward pass, which run on the main stream: it stays there as well)
+        if again or any(not p.is_leaf or p.grad is not None or self._hooked(p) for p in live):
             # main-stream fallback.  Weight gradients of this pass may still be running on the side stream: autograd adds
             # the first use's gradient of a re-used parameter to this one ON THE MAIN STREAM before the end-of-pass join,
             # a hook reads it the moment it is returned, and the library's slab workspace serves one launch at a time --
@@ -521,6 +523,30 @@ class ToStorage(torch.autograd.Function):
         return g.float(), None
 
 
+class FromStorage(torch.autograd.Function):
+    """storage dtype -> fp32 (``pai_cast``) with the gradient cast to the storage dtype: the last step of a network whose
+    output leaves as fp32."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.dtype = x.dtype
+        if x.dtype == torch.float32:
+            return x
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        ops.cast(x.contiguous(), out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g.dtype != torch.float32:
+            raise ops.PaiError(f"FromStorage: gradient of {g.dtype} for an fp32 output")
+        if ctx.dtype == torch.float32:
+            return g
+        out = torch.empty(g.shape, dtype=ctx.dtype, device=g.device)
+        ops.cast(g.contiguous(), out)
+        return out
+
+
 class MaxPool2(torch.autograd.Function):
     """nn.MaxPool2d(2) (reference models/res_unet.py:199)."""
 
@@ -561,6 +587,28 @@ class Upsample2(torch.autograd.Function):
         N, H, W, C = ctx.shape
         dx = torch.empty(N, H, W, C, dtype=g.dtype, device=g.device)
         ops.upsample2_bwd(g.dtype, g.contiguous(), N, H, W, C, dx)
+        return dx
+
+
+class AvgPool2(torch.autograd.Function):
+    """nn.AvgPool2d(2) (reference models/guided_diffusion/unet.py:98, Downsample(use_conv=False))."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _check(x)
+        N, H, W, C = x.shape
+        if H % 2 or W % 2:
+            raise ops.PaiError(f"AvgPool2: a {H} x {W} level cannot be halved")
+        out = torch.empty(N, H // 2, W // 2, C, dtype=x.dtype, device=x.device)
+        ops.avgpool2(x.dtype, x, N, H, W, C, out)
+        ctx.shape = (N, H, W, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        N, H, W, C = ctx.shape
+        dx = torch.empty(N, H, W, C, dtype=g.dtype, device=g.device)
+        ops.avgpool2_bwd(g.dtype, g.contiguous(), N, H, W, C, dx)
         return dx
 
 
@@ -1002,6 +1050,46 @@ class GELU(torch.autograd.Function):
         dz = torch.empty_like(z)
         ops.gelu_bwd(z.dtype, g.contiguous(), z, dz)
         return dz
+
+
+class SiLU(torch.autograd.Function):
+    """x * sigmoid(x) on a token tensor [M, D] (the SiLUs of the guided-diffusion embedding path, reference
+    models/guided_diffusion/unet.py:395-399,160-166): ``pai_affine_act`` with unit coefficients forward, ``pai_silu_bwd``
+    backward.  ``ones`` / ``zeros``: fp32 [D] coefficient vectors of the caller (no fill launch per call)."""
+
+    @staticmethod
+    def forward(ctx, u, ones, zeros):
+        _check_tokens(u)
+        M, D = u.shape
+        out = torch.empty_like(u)
+        ops.affine_act(u.dtype, u, 1, M, D, ones, zeros, False, ops.ACT_SILU, out)
+        ctx.save_for_backward(u)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (u,) = ctx.saved_tensors
+        g = g.contiguous()
+        du = torch.empty_like(u)
+        ops.silu_bwd(u.dtype, g, u, du)
+        return du, None, None
+
+
+class SplitCols(torch.autograd.Function):
+    """[M, sum(sizes)] -> one contiguous [M, size] copy per entry of ``sizes`` (the FiLM ``scale | shift`` columns of every
+    ResBlock out of the one GEMM over the concatenated ``emb_layers``); the backward is one concatenation.  Data movement
+    only."""
+
+    @staticmethod
+    def forward(ctx, x, sizes):
+        _check_tokens(x)
+        if sum(sizes) != x.shape[1]:
+            raise ops.PaiError(f"SplitCols: {x.shape[1]} columns for sizes that sum to {sum(sizes)}")
+        return tuple(t.contiguous() for t in torch.split(x, list(sizes), dim=1))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        return torch.cat(gs, dim=1), None
 
 
 class MHACore(torch.autograd.Function):

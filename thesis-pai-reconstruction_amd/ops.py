@@ -1193,6 +1193,20 @@ def avgpool2(dtype, x, N, H, W, C_, out):
     L.check(L.load().pai_avgpool2(code_of(dtype), _p(x, dtype), N, H, W, C_, _p(out, dtype), _stream()), "pai_avgpool2")
 
 
+def avgpool2_bwd(dtype, dout, N, H, W, C_, dx):
+    """dx [N][H][W][C] = dout [N][H/2][W/2][C] / 4 at the four positions of every window (pai_avgpool2_bwd)."""
+    L.check(L.load().pai_avgpool2_bwd(code_of(dtype), _p(dout, dtype), int(N), int(H), int(W), int(C_), _p(dx, dtype),
+                                      _stream()), "pai_avgpool2_bwd")
+
+
+def silu_bwd(dtype, g, u, du):
+    """du = g * SiLU'(u) element-wise; du may be g (pai_silu_bwd)."""
+    if g.numel() != u.numel() or du.numel() != u.numel():
+        raise PaiError("silu_bwd: g, u and du differ in size")
+    L.check(L.load().pai_silu_bwd(code_of(dtype), _p(g, dtype), _p(u, dtype), int(u.numel()), _p(du, dtype), _stream()),
+            "pai_silu_bwd")
+
+
 def gamma_embedding(gammas, N, dim, out):
     """out [N][dim] (fp32 or bf16) = [cos(g f) | sin(g f)] of the fp32 noise levels ``gammas`` (pai_gamma_embedding)."""
     L.check(L.load().pai_gamma_embedding(code_of(out.dtype), _p(gammas, torch.float32), int(N), int(dim), _p(out), _stream()),
