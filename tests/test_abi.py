@@ -120,6 +120,44 @@ def test_kernel_dispatch_table_without_gpu(pai):
         assert tuple(ops.conv_kernel_name(d, op) for op in (0, 1, 2)) == want, layer
 
 
+def test_rectangular_dispatch_table_without_gpu(pai):
+    """The rows of tests/test_gpu_conv_exact.py with H != W (RECT_CASES, THIN_RECT) are there for the kernel each one
+    names: pinned here on the host, without a workspace or scratch (the un-split names; a thin layer's narrow side then
+    reports the row-dot kernel, the GPU test registers the scratch and asserts the thin family for it), so that a change of
+    the selection cannot move a row to another kernel and leave the GPU test green on that one.  And the table as a whole
+    reaches every stride-2 matrix-core kernel."""
+    import importlib.util
+    import sys
+    import torch
+    from thesis_pai_reconstruction_amd import ops
+    sys.path.insert(0, os.path.join(ROOT, "tests"))         # its helper module (_gpu_util), as under pytest's rootdir
+    try:
+        spec = importlib.util.spec_from_file_location("_gpu_conv_exact_cases", os.path.join(ROOT, "tests", "test_gpu_conv_exact.py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+    finally:
+        sys.path.remove(os.path.join(ROOT, "tests"))
+    reached = set()
+    for name, tr, N, (H, W), C1, C2, Cout, relu, want in mod.RECT_CASES:
+        assert H != W, name
+        d = ops.make_desc(torch.bfloat16, tr, N, H, W, C1, C2, Cout, 2, relu, relu if C2 else 0, ops.ACT_NONE)
+        got = tuple(ops.conv_kernel_name(d, op) for op in (0, 1, 2))
+        unsplit = tuple(w[1] if isinstance(w, tuple) else w for w in want)        # SPLIT = (split, un-split)
+        assert got == unsplit, (name, got)
+        reached.update(got)
+    assert reached >= {"gg_fwd_patch_k<128, 128, true>", "gg_fwd_patch_k<128, 64, false>", "gg_fwd_patch_k<256, 128, true>",
+                       "gg_fwd_patch1_k<256, 64, false>", "gg_fwd_mfma_k<128, 128, false, false, 64>",
+                       "gg_fwd_mfma_k<128, 64, false, false, 64>", "gg_wgrad_patch3_k<128, 64, 16>", "gg_wgrad_patch3_k<64, 128, 16>",
+                       "gg_wgrad_patch3_k<128, 64, 8>", "gg_wgrad_mfma_k<64>", "gg_simt"}, sorted(reached)
+    assert set(mod.RECT_FAMILY) <= {c[0] for c in mod.RECT_CASES}
+    thin, rowdot = "thin_mfma_bf16", "gg_rowdot"
+    for name, tr, N, (H, W), C1, C2, Cout in mod.THIN_RECT:
+        assert H != W, name
+        d = ops.make_desc(torch.bfloat16, tr, N, H, W, C1, C2, Cout, 2, 0, 0, ops.ACT_NONE if tr else ops.ACT_LRELU)
+        got = tuple(ops.conv_kernel_name(d, op) for op in (0, 1, 2))
+        assert got == ((rowdot, thin, thin) if tr else (thin, rowdot, thin)), (name, got)
+
+
 def test_conv_selection_switches_without_gpu(pai):
     """The forward and weight-gradient switches of the selection are tunables: each one moves the REPORTED kernel of
     encoders[2] (configs[1]) to the next kernel of its chain, and unsetting it brings the pinned default back.  The names

@@ -48,6 +48,20 @@ CASES = [
     # long reduction, few output rows: split-K slabs + finish kernel in forward and input gradient
     ("enc_splitk", 0, 2, 4, 8, 8, 256, 0, 256, 0, 0),
     ("dec_splitk", 1, 2, 4, 4, 4, 256, 256, 256, 1, 1),
+    # H != W (every stride-2 row above is square): wide, tall and a side that is no power of two, on the patch kernels
+    # (tile grids 1 x 1 ... 3 x 1 / 1 x 3) and on the tile kernels; in fp32 these are gg_simt's stride-2 rectangles
+    ("rect_enc_wide", 0, 2, 2, 16, 32, 64, 0, 128, 0, 0),
+    ("rect_enc_tall", 0, 2, 2, 32, 16, 128, 0, 128, 0, 0),
+    ("rect_enc_npot", 0, 2, 3, 48, 32, 64, 0, 128, 0, 0),
+    ("rect_enc_npot_tile", 0, 2, 3, 24, 40, 128, 0, 64, 0, 0),
+    ("rect_dec_wide", 1, 2, 2, 16, 32, 64, 64, 128, 1, 1),
+    ("rect_dec_tall", 1, 2, 2, 32, 16, 128, 128, 64, 0, 1),
+    ("rect_dec_npot", 1, 2, 2, 8, 48, 64, 64, 128, 1, 1),
+    ("rect_dec_npot_tile", 1, 2, 3, 12, 20, 128, 64, 64, 0, 1),
+    # the thin layers: LeakyReLU copy, fp32 output and the only_c2 gradient on H != W
+    ("rect_enc0", 0, 2, 3, 24, 40, 1, 0, 64, 0, 0),
+    ("rect_disc0", 0, 2, 2, 48, 32, 1, 1, 64, 0, 0),
+    ("rect_head", 1, 2, 2, 24, 16, 64, 64, 1, 1, 1),
 ]
 
 
@@ -61,6 +75,9 @@ BF16_FAMILY = {
     "odd_batch_rgb": (0, 0, 0), "enc_patch": (2, 3, 2), "dec_patch": (2, 3, 2), "enc_patch256": (2, 3, 2),
     "dec_patch256": (2, 2, 2), "enc0_wide": (4, 1, 4), "disc0_wide": (4, 1, 4), "head_wide": (1, 4, 4),
     "dec_patch256x64": (3, 2, 3), "enc_dgrad256": (2, 2, 2), "enc_splitk": (2, 2, 2), "dec_splitk": (2, 2, 2),
+    "rect_enc_wide": (2, 3, 2), "rect_enc_tall": (2, 2, 2), "rect_enc_npot": (2, 3, 0), "rect_enc_npot_tile": (3, 2, 0),
+    "rect_dec_wide": (2, 3, 2), "rect_dec_tall": (3, 2, 3), "rect_dec_npot": (2, 3, 0), "rect_dec_npot_tile": (3, 3, 0),
+    "rect_enc0": (4, 1, 4), "rect_disc0": (4, 1, 4), "rect_head": (1, 4, 4),
 }
 
 

@@ -42,10 +42,116 @@ CASES = [
     ("cfg2_D3", 0, 128, 32, 256, 0, 512, 0, ("gg_fwd_patch_k<256, 128, true>", "gg_fwd_patch_k<256, 128, true>", "gg_wgrad_patch3_k<128, 64, 16>")),
 ]
 
+# ---- the same kernels on images with H != W ---------------------------------------------------------------------------
+# CASES has H == W and powers of two throughout: there lw == lh, lsw == lsh, ldw == ldh (finish_gg, csrc/api.hip) and
+# TY == TX (patch_geo_raw), so a swapped pair, or a row stride taken from the wrong side, computes the same thing.  Here the
+# H field is an (H, W) pair.  Wide / tall powers of two keep the SHIFT decode with lw != lh (and lsw != lsh, ldw != ldh);
+# a side that is no power of two sets every logarithm to -1 and moves tile, thin and weight-gradient kernels to the DIVISION
+# decode (the weight gradient to gg_simt), while the patch kernels still take it if the tile grid divides: grids 3 x 2,
+# 2 x 3 and 3 x 5 make TY != TX with neither a power of two.  Names: pai_conv_kernel_name without a workspace.
+P128 = ("gg_fwd_patch_k<128, 128, true>", "gg_fwd_patch_k<128, 64, false>")
+T128, T64 = "gg_fwd_mfma_k<128, 128, false, false, 64>", "gg_fwd_mfma_k<128, 64, false, false, 64>"
+P256, P1 = "gg_fwd_patch_k<256, 128, true>", "gg_fwd_patch1_k<256, 64, false>"
+WG_A, WG_B, WG_8 = "gg_wgrad_patch3_k<128, 64, 16>", "gg_wgrad_patch3_k<64, 128, 16>", "gg_wgrad_patch3_k<128, 64, 8>"
+RECT_CASES = [
+    ("conv_wide", 0, 2, (32, 64), 64, 0, 128, 0, P128 + (WG_A,)),
+    ("conv_tall", 0, 2, (64, 32), 64, 0, 128, 0, P128 + (WG_A,)),
+    ("conv_h48", 0, 2, (48, 64), 64, 0, 128, 0, P128 + ("gg_simt",)),             # tile grid 3 x 2
+    ("conv_w96", 0, 2, (32, 96), 64, 0, 128, 0, P128 + ("gg_simt",)),             # tile grid 2 x 3
+    ("conv_untiled", 0, 3, (12, 40), 64, 0, 128, 0, (T128, T64, "gg_simt")),      # 6 x 20 output pixels: no patch tiling
+    ("conv_untiled64", 0, 3, (20, 12), 64, 0, 64, 0, (T64, T64, "gg_simt")),
+    ("conv_rows8", 0, 2, (64, 16), 64, 0, 128, 0, (T128, T64, WG_8)),             # 8-pixel rows, 32 of them
+    ("conv_4rows", 0, 4, (8, 32), 128, 0, 128, 0, (T128, T128, WG_A)),            # 4 output rows of 16 pixels
+    ("convT_wide", 1, 2, (16, 32), 64, 64, 128, 1, P128 + (WG_A,)),
+    ("convT_tall", 1, 2, (32, 16), 64, 64, 128, 1, P128 + (WG_A,)),
+    ("convT_h24", 1, 2, (24, 32), 64, 64, 128, 1, P128 + ("gg_simt",)),
+    ("convT_w48", 1, 2, (16, 48), 64, 64, 128, 1, P128 + ("gg_simt",)),
+    ("convT_untiled", 1, 3, (6, 10), 128, 64, 64, 1, (T64, T64, "gg_simt")),
+    ("convT_rows8", 1, 2, (32, 8), 64, 0, 128, 1, (T128, T64, WG_8)),
+    ("convT64_wide", 1, 2, (8, 32), 128, 128, 64, 1, (P128[1], P128[0], WG_B)),
+    ("convT64_tall", 1, 2, (32, 16), 128, 128, 64, 1, (P128[1], P128[0], WG_B)),
+    # 16 x 16-pixel tiles are chosen from 512 tiles on (768 for the one-wave-column form): the smallest layers that get there
+    ("p256_conv_wide", 0, 8, (128, 256), 64, 0, 256, 0, (P256, P1, WG_A)),
+    ("p256_conv_tall", 0, 8, (256, 128), 64, 0, 256, 0, (P256, P1, WG_A)),
+    ("p256_conv_3x5", 0, 18, (96, 160), 64, 0, 256, 0, (P256, P1, "gg_simt")),
+    ("p256_convT_wide", 1, 16, (32, 64), 128, 0, 128, 1, (P256, P128[0], WG_A)),
+    ("p256_convT_tall", 1, 16, (64, 32), 128, 0, 128, 1, (P256, P128[0], WG_A)),
+    ("p256_convT_3x5", 1, 9, (48, 80), 128, 0, 128, 1, (P256, P128[0], "gg_simt")),
+    ("p1_wide", 1, 24, (32, 64), 128, 128, 64, 1, (P1, P128[0], WG_B)),
+    ("p1_3x5", 1, 13, (48, 80), 128, 128, 64, 1, (P1, P128[0], "gg_simt")),
+    # the bottleneck: split over K once the workspace is registered (asserted in the with_workspace run)
+    ("bn_wide", 0, 4, (4, 16), 256, 0, 256, 0, (SPLIT, SPLIT, "gg_wgrad_mfma_k<64>")),
+    ("bn_tall", 0, 4, (16, 4), 256, 0, 256, 0, (SPLIT, SPLIT, "gg_wgrad_mfma_k<64>")),
+    ("bnT_wide", 1, 4, (2, 8), 256, 256, 256, 1, (SPLIT, SPLIT, "gg_wgrad_mfma_k<64>")),
+    ("bnT_tall", 1, 4, (8, 2), 256, 256, 256, 1, (SPLIT, SPLIT, "gg_wgrad_mfma_k<64>")),
+    ("bnT_6x4", 1, 4, (6, 4), 256, 256, 256, 1, (SPLIT, SPLIT, "gg_simt")),
+]
+# kernel family of a RECT_CASES row in forward AND input gradient, for the tests of the fused stores below.  Those tests
+# register the split-K workspace, with which the cost model of fwd_cfg splits the small patch and tile rows as well: the
+# tunable fwd_ksplit = 1 holds "patch" and "tile" rows on the un-split kernel the table names
+RECT_FAMILY = {"conv_wide": "patch", "conv_tall": "patch", "conv_h48": "patch", "conv_w96": "patch", "convT_wide": "patch",
+               "convT_tall": "patch", "convT_h24": "patch", "p256_convT_3x5": "patch", "p256_conv_tall": "patch",
+               "conv_untiled": "tile", "conv_rows8": "tile", "conv_4rows": "tile", "convT_untiled": "tile", "convT_rows8": "tile",
+               "bn_wide": "split", "bn_tall": "split", "bnT_wide": "split", "bnT_tall": "split", "bnT_6x4": "split"}
+
+
+def _case(name):
+    return next(c for c in CASES + RECT_CASES if c[0] == name)
+
+
+class _pinned:
+    """Holds a RECT_CASES row on the kernel family RECT_FAMILY names while a test with the workspace registered runs it;
+    rows of CASES (no entry) run as they always did.  check(d, op) asserts the family the launch reports."""
+
+    def __init__(self, ops, name):
+        self.ops, self.family = ops, RECT_FAMILY.get(name)
+
+    def __enter__(self):
+        if self.family in ("patch", "tile"):
+            self.ops.set_tunable("fwd_ksplit", 1)
+        return self
+
+    def __exit__(self, *exc):
+        if self.family in ("patch", "tile"):
+            self.ops.set_tunable("fwd_ksplit")
+
+    def check(self, d, op):
+        got = self.ops.conv_kernel_name(d, op)
+        if self.family == "patch":
+            assert got.startswith("gg_fwd_patch"), got
+        elif self.family == "tile":
+            assert got in (T128, T64), got
+        elif self.family == "split":
+            assert got == SPLIT[0], got
+
 
 def _ints(shape, seed, lo=-2, hi=2):
     g = torch.Generator().manual_seed(seed)
     return torch.randint(lo, hi + 1, shape, generator=g).float()
+
+
+def _hw(side):
+    """The image field of a case: one side (a square image) or an (H, W) pair."""
+    return (side, side) if isinstance(side, int) else tuple(side)
+
+
+def _out_hw(tr, H, W):
+    return (H * 2, W * 2) if tr else (H // 2, W // 2)
+
+
+def _first_diff(got, want):
+    """Index ((n, c, y, x) of an image tensor) of the first element that differs, both values and the number of
+    differing elements: the message of a failed bit comparison."""
+    bad = (got != want) & ~(torch.isnan(got) & torch.isnan(want))
+    idx = bad.nonzero()
+    if not len(idx):
+        return None
+    i = tuple(int(v) for v in idx[0])
+    return i, float(got[i]), float(want[i]), int(bad.sum())
+
+
+def _same(got, want, *what):
+    assert torch.equal(got, want), what + (_first_diff(got, want),)
 
 
 def _named(ops, d, op, want):
@@ -66,23 +172,39 @@ def _reference(tr, x1, x2, w, dy, relu, bias=None):
     return y.detach(), x.grad, wr.grad
 
 
+_DATA = {}
+
+
+def _case_data(tr, N, H, W, C1, C2, Cout, relu):
+    """Inputs and PyTorch-CPU reference of one shape: computed once, kept for the runs of the same shape that follow
+    (named / with_workspace, the tunable settings of one row) and never written to."""
+    key = (tr, N, H, W, C1, C2, Cout, relu)
+    if key not in _DATA:
+        _DATA.clear()
+        Cin = C1 + C2
+        OH, OW = _out_hw(tr, H, W)
+        x1 = _ints((N, C1, H, W), 1)
+        x2 = _ints((N, C2, H, W), 2) if C2 else None
+        w = _ints((Cin, Cout, 4, 4) if tr else (Cout, Cin, 4, 4), 3)
+        dy = _ints((N, Cout, OH, OW), 5)
+        bias = _ints((Cout,), 7, -3, 3)           # the bias add of the epilogue is part of what is pinned
+        _DATA[key] = (x1, x2, w, dy, bias) + _reference(tr, x1, x2, w, dy, relu, bias)
+    return _DATA[key]
+
+
 def _run_case(pai, case, tunables=(), workspace=True):
     """workspace=False: a handle WITHOUT split-K workspace, the setting the kernel names of CASES were recorded in
     (pai_conv_kernel_name on the host); True: the default handle with the workspace registered, where the library may
     pick the split-K kernels for the smaller cases -- same bits either way."""
     from thesis_pai_reconstruction_amd import ops
     name, tr, N, H, C1, C2, Cout, relu, names = case
+    H, W = _hw(H)
     Cin, dt = C1 + C2, torch.bfloat16
-    x1 = _ints((N, C1, H, H), 1)
-    x2 = _ints((N, C2, H, H), 2) if C2 else None
-    w = _ints((Cin, Cout, 4, 4) if tr else (Cout, Cin, 4, 4), 3)
-    OH = H * 2 if tr else H // 2
-    dy = _ints((N, Cout, OH, OH), 5)
-    bias = _ints((Cout,), 7, -3, 3)           # the bias add of the epilogue is part of what is pinned
-    y_ref, dx_ref, dw_ref = _reference(tr, x1, x2, w, dy, relu, bias)
+    OH, OW = _out_hw(tr, H, W)
+    x1, x2, w, dy, bias, y_ref, dx_ref, dw_ref = _case_data(tr, N, H, W, C1, C2, Cout, relu)
     assert float(y_ref.abs().max()) < 2 ** 24 and float(dw_ref.abs().max()) < 2 ** 24     # exact in fp32
 
-    d = ops.make_desc(dt, tr, N, H, H, C1, C2, Cout, 2, relu, relu if C2 else 0, ops.ACT_NONE)
+    d = ops.make_desc(dt, tr, N, H, W, C1, C2, Cout, 2, relu, relu if C2 else 0, ops.ACT_NONE)
     default = ops.handle_for(dev())
     bare = None
     if workspace:
@@ -103,11 +225,11 @@ def _run_case(pai, case, tunables=(), workspace=True):
         used = []
         # forward
         used.append(_named(ops, d, 0, names[0]) if check_names else ops.conv_kernel_name(d, 0))
-        y = torch.empty(N * OH * OH * Cout, dtype=dt, device=dev())
+        y = torch.empty(N * OH * OW * Cout, dtype=dt, device=dev())
         stats = torch.zeros(ops.bn_stats_buffer_rows(ops.conv_fwd_stats_rows_max(d)) * 2 * Cout, device=dev())
         ops.conv_fwd(d, X1, X2, wf, bias.to(dev()), y_raw=y, stats=stats)
         torch.cuda.synchronize()
-        assert torch.equal(from_nhwc(y, N, OH, OH, Cout), y_ref.bfloat16().float()), (name, "forward")
+        _same(from_nhwc(y, N, OH, OW, Cout), y_ref.bfloat16().float(), name, "forward")
         rows = ops.conv_fwd_stats_rows(d)
         st = stats[:rows * 2 * Cout].view(rows, 2, Cout).double().sum(0).cpu()
         # BatchNorm partial sums come from the fp32 accumulators: integers, exact while the row sums stay below 2^24
@@ -115,19 +237,19 @@ def _run_case(pai, case, tunables=(), workspace=True):
         assert torch.equal(st[0], yd.sum((0, 2, 3))) or float((st[0] - yd.sum((0, 2, 3))).abs().max()) <= 1e-6 * float(yd.abs().sum()), name
         # input gradient, split over the two sources
         used.append(_named(ops, d, 1, names[1]) if check_names else ops.conv_kernel_name(d, 1))
-        dx1 = torch.empty(N * H * H * C1, dtype=dt, device=dev())
-        dx2 = torch.empty(N * H * H * C2, dtype=dt, device=dev()) if C2 else None
+        dx1 = torch.empty(N * H * W * C1, dtype=dt, device=dev())
+        dx2 = torch.empty(N * H * W * C2, dtype=dt, device=dev()) if C2 else None
         ops.conv_dgrad(d, DY, wd, dx1, dx2)
         torch.cuda.synchronize()
-        assert torch.equal(from_nhwc(dx1, N, H, H, C1), dx_ref[:, :C1].bfloat16().float()), (name, "dgrad x1")
+        _same(from_nhwc(dx1, N, H, W, C1), dx_ref[:, :C1].bfloat16().float(), name, "dgrad x1")
         if C2:
-            assert torch.equal(from_nhwc(dx2, N, H, H, C2), dx_ref[:, C1:].bfloat16().float()), (name, "dgrad x2")
+            _same(from_nhwc(dx2, N, H, W, C2), dx_ref[:, C1:].bfloat16().float(), name, "dgrad x2")
         # weight gradient (fp32, accumulating)
         used.append(_named(ops, d, 2, names[2]) if check_names else ops.conv_kernel_name(d, 2))
         dw = torch.zeros(wm.numel(), dtype=torch.float32, device=dev())
         ops.conv_wgrad(d, X1, X2, DY, dw, None)
         torch.cuda.synchronize()
-        assert torch.equal(unpack_fwd(dw, Cout, Cin, bool(tr)), dw_ref), (name, "wgrad")
+        _same(unpack_fwd(dw, Cout, Cin, bool(tr)), dw_ref, name, "wgrad")
         return used
     finally:
         for k, _ in tunables:
@@ -149,6 +271,17 @@ def test_mfma_kernels_bit_exact_on_integer_data(pai, case, workspace):
         assert used[0] == SPLIT[0] and used[1] == SPLIT[0], used
 
 
+@pytest.mark.parametrize("workspace", [False, True], ids=["named", "with_workspace"])
+@pytest.mark.parametrize("case", RECT_CASES, ids=[c[0] for c in RECT_CASES])
+def test_mfma_kernels_bit_exact_on_rectangular_images(pai, case, workspace):
+    """RECT_CASES through the body of the test above: forward with bias and BatchNorm partial statistics, both source
+    gradients and the accumulating weight gradient against PyTorch-CPU, bit for bit, on the kernels named (asserted in the
+    run without a workspace) and with the workspace registered, where the bottleneck rows must run split over K."""
+    used = _run_case(pai, case, workspace=workspace)
+    if workspace and case[0].startswith("bn"):
+        assert used[0] == SPLIT[0] and used[1] == SPLIT[0], used
+
+
 # ---- the pipelined K loop of gg_wgrad_patch3_k: every way a pixel split can end ---------------------------------------
 # The loop runs pairs of steps while two more follow and finishes with 1-3 steps whose look-ahead (next fragments, fill after
 # next) is switched off one by one; a split of ONE step skips the second fill of the prologue.  (tr, N, H, C1, C2, Cout,
@@ -157,13 +290,18 @@ def test_mfma_kernels_bit_exact_on_integer_data(pai, case, workspace):
 PIPE_TAILS = [(0, 1, 32, 64, 0, 128, 0, 16), (0, 2, 32, 64, 0, 128, 0, 12), (0, 2, 32, 64, 0, 128, 0, 8), (0, 3, 32, 64, 0, 128, 0, 20),
               (0, 5, 32, 64, 0, 128, 0, 12), (0, 7, 32, 128, 0, 128, 0, 24),
               (1, 1, 16, 128, 128, 64, 1, 16), (1, 3, 16, 128, 128, 64, 1, 40), (1, 5, 16, 128, 128, 64, 1, 24),
-              (0, 5, 16, 64, 0, 128, 0, 12), (1, 3, 8, 128, 0, 128, 1, 24)]
+              (0, 5, 16, 64, 0, 128, 0, 12), (1, 3, 8, 128, 0, 128, 1, 24),
+              # H != W: the pixel decode of a split (lw != lh) under the same split lengths -- wide and tall for the two
+              # 16-pixel forms; the 8 x 8-pixel form takes 8-pixel rows of at least 8 (lw == 3, lh >= 3): tall only
+              (0, 2, (32, 64), 64, 0, 128, 0, 12), (0, 3, (64, 32), 64, 0, 128, 0, 20), (0, 5, (16, 64), 64, 0, 128, 0, 12),
+              (1, 3, (16, 32), 128, 128, 64, 1, 40), (1, 5, (32, 16), 128, 128, 64, 1, 24),
+              (0, 5, (64, 16), 64, 0, 128, 0, 12), (1, 3, (32, 8), 128, 0, 128, 1, 24), (1, 3, (16, 8), 128, 0, 128, 1, 24)]
 
 
 @pytest.mark.parametrize("cfg", PIPE_TAILS, ids=str)
 def test_pipelined_weight_gradient_loop_on_every_split_length(pai, cfg):
     from thesis_pai_reconstruction_amd import ops
-    tr, N, H, C1, C2, Cout, relu, target = cfg
+    tr, N, H, C1, C2, Cout, relu, target = cfg       # H: a side or an (H, W) pair, as in CASES
     case = ("pipe_tail", tr, N, H, C1, C2, Cout, relu, None)
     for pipe in (1, 0):
         used = _run_case(pai, case, tunables=(("wgrad3_target", target), ("wgrad3_minrows", 64), ("wgrad3_pipe", pipe)))
@@ -171,7 +309,8 @@ def test_pipelined_weight_gradient_loop_on_every_split_length(pai, cfg):
 
 
 OLD_WGRAD = {"enc_patch": "gg_wgrad_patch_k<128>", "dec_patch": "gg_wgrad_patch_k<128>", "dec_patch256x64": "gg_wgrad_patch_k<64>",
-             "cfg2_dec5": "gg_wgrad_patch_k<128>"}
+             "cfg2_dec5": "gg_wgrad_patch_k<128>", "conv_wide": "gg_wgrad_patch_k<128>", "conv_tall": "gg_wgrad_patch_k<128>",
+             "convT64_wide": "gg_wgrad_patch_k<64>", "convT64_tall": "gg_wgrad_patch_k<64>"}
 
 
 @pytest.mark.parametrize("name", sorted(OLD_WGRAD))
@@ -179,13 +318,13 @@ def test_previous_weight_gradient_kernels_stay_exact(pai, name):
     """gg_wgrad_patch_k (round 1-2; still the kernel of layers gg_wgrad_patch3_k does not take, e.g. 32-channel
     multiples): tunable wgrad3 = 0 routes the same cases back to it."""
     from thesis_pai_reconstruction_amd import ops
-    case = next(c for c in CASES if c[0] == name)
+    case = _case(name)
     used = _run_case(pai, case, tunables=(("wgrad3", 0),))
     assert used[2] == OLD_WGRAD[name], used
     ops.set_tunable("wgrad3", 0)
     ops.set_tunable("wgrad_slab", 0)
     try:
-        d = ops.make_desc(torch.bfloat16, case[1], case[2], case[3], case[3], case[4], case[5], case[6], 2, 0, 0, ops.ACT_NONE)
+        d = ops.make_desc(torch.bfloat16, case[1], case[2], *_hw(case[3]), case[4], case[5], case[6], 2, 0, 0, ops.ACT_NONE)
         assert ops.conv_wgrad_workspace_bytes(d) >= 0
     finally:
         ops.set_tunable("wgrad3")
@@ -193,25 +332,27 @@ def test_previous_weight_gradient_kernels_stay_exact(pai, name):
 
 
 @pytest.mark.parametrize("slab", [1, 0], ids=["slabs", "atomics"])
-@pytest.mark.parametrize("name", ["enc_patch256", "dec_patch256x64", "cfg2_D1", "cfg2_dec4", "cfg2_enc4", "cfg2_dec3"])
+@pytest.mark.parametrize("name", ["enc_patch256", "dec_patch256x64", "cfg2_D1", "cfg2_dec4", "cfg2_enc4", "cfg2_dec3",
+                                  "conv_wide", "conv_tall", "convT64_wide", "convT64_tall", "conv_rows8"])
 def test_weight_gradient_bias_and_overwrite(pai, name, slab):
     """gg_wgrad_patch3_k with a bias gradient (column sums of dY taken from the fragments every wave holds, spread over
     the workgroups that share a dY tile) and through pai_conv_wgrad_overwrite (dW / dbias need no zero fill: the slab sum,
     or the single writer of an un-split tile, stores them) -- exact on integer data, with the pixel splits meeting through
     slabs and through fp32 atomics."""
     from thesis_pai_reconstruction_amd import ops
-    case = next(c for c in CASES if c[0] == name)
+    case = _case(name)
     _, tr, N, H, C1, C2, Cout, relu, names = case
+    H, W = _hw(H)
     Cin, dt = C1 + C2, torch.bfloat16
-    x1 = _ints((N, C1, H, H), 1)
-    x2 = _ints((N, C2, H, H), 2) if C2 else None
-    OH = H * 2 if tr else H // 2
-    dy = _ints((N, Cout, OH, OH), 5)
+    x1 = _ints((N, C1, H, W), 1)
+    x2 = _ints((N, C2, H, W), 2) if C2 else None
+    OH, OW = _out_hw(tr, H, W)
+    dy = _ints((N, Cout, OH, OW), 5)
     w = torch.zeros((Cin, Cout, 4, 4) if tr else (Cout, Cin, 4, 4))
     _, _, dw_ref = _reference(tr, x1, x2, w, dy, relu)
     db_ref = dy.sum((0, 2, 3))
     assert float(dw_ref.abs().max()) < 2 ** 24 and float(db_ref.abs().max()) < 2 ** 24
-    d = ops.make_desc(dt, tr, N, H, H, C1, C2, Cout, 2, relu, relu if C2 else 0, ops.ACT_NONE)
+    d = ops.make_desc(dt, tr, N, H, W, C1, C2, Cout, 2, relu, relu if C2 else 0, ops.ACT_NONE)
     ops.ensure_wgrad_workspace([d], dev())
     ops.set_tunable("wgrad_slab", slab)
     try:
@@ -239,9 +380,10 @@ def test_two_handles_keep_their_own_buffers(pai):
     from thesis_pai_reconstruction_amd import ops
     case = next(c for c in CASES if c[0] == "enc_splitk")
     name, tr, N, H, C1, C2, Cout, relu, _ = case
+    W = H
     dt = torch.bfloat16
-    d = ops.make_desc(dt, tr, N, H, H, C1, C2, Cout, 2, 0, 0, ops.ACT_NONE)
-    x1, w = _ints((N, C1, H, H), 1), _ints((Cout, C1, 4, 4), 3)
+    d = ops.make_desc(dt, tr, N, H, W, C1, C2, Cout, 2, 0, 0, ops.ACT_NONE)
+    x1, w = _ints((N, C1, H, W), 1), _ints((Cout, C1, 4, 4), 3)
     y_ref = F.conv2d(x1, w, None, stride=2, padding=1).bfloat16().float()
     wm = fwd_pack(w, False)
     wf = torch.empty(wm.numel(), dtype=dt, device=dev())
@@ -277,7 +419,12 @@ def test_two_handles_keep_their_own_buffers(pai):
 # (case of CASES, act1, act2, affine): decoder form (producer read through ReLU, no second gradient) and encoder form
 # (LeakyReLU on the encoder path + the skip decoder's gradient through ReLU), on the kernels the benchmark runs
 DGRAD_BN = [("dec_patch256", 2, 0, True), ("enc_dgrad256", 1, 2, True), ("cfg2_enc2", 1, 2, True), ("dec_splitk", 2, 0, True),
-            ("enc_patch256", 1, 0, False)]
+            ("enc_patch256", 1, 0, False),
+            # RECT_CASES rows: z and add are read, and the partial rows written, by output-pixel index -- wide, tall and a
+            # side that is no power of two for the patch kernels, the un-split tile kernel and the split-K finish
+            ("convT_wide", 2, 0, True), ("conv_tall", 1, 2, True), ("conv_h48", 1, 2, True), ("p256_convT_3x5", 2, 0, True),
+            ("p256_conv_tall", 1, 0, False), ("conv_4rows", 1, 2, True), ("conv_rows8", 1, 0, False), ("conv_untiled", 1, 2, True),
+            ("convT_untiled", 2, 0, True), ("bn_wide", 1, 2, True), ("bnT_tall", 2, 0, True), ("bnT_6x4", 2, 0, True)]
 
 
 @pytest.mark.parametrize("cfg", DGRAD_BN, ids=[c[0] for c in DGRAD_BN])
@@ -289,19 +436,20 @@ def test_fused_producer_backward_bit_exact(pai, cfg):
     kernels)."""
     from thesis_pai_reconstruction_amd import ops
     name, act1, act2, affine = cfg
-    case = next(c for c in CASES if c[0] == name)
+    case = _case(name)
     _, tr, N, H, C1, C2, Cout, relu, _ = case
+    H, W = _hw(H)
     Cin, dt = C1 + C2, torch.bfloat16
-    OH = H * 2 if tr else H // 2
+    OH, OW = _out_hw(tr, H, W)
     w = _ints((Cin, Cout, 4, 4) if tr else (Cout, Cin, 4, 4), 3)
-    dy = _ints((N, Cout, OH, OH), 5)
+    dy = _ints((N, Cout, OH, OW), 5)
     # input gradient w.r.t. the layer's (concatenated) input, exact integers
-    x = torch.zeros(N, Cin, H, H, requires_grad=True)
+    x = torch.zeros(N, Cin, H, W, requires_grad=True)
     y = F.conv_transpose2d(x, w, None, stride=2, padding=1) if tr else F.conv2d(x, w, None, stride=2, padding=1)
     y.backward(dy)
     g = x.grad[:, :C1].bfloat16().float()                      # what the kernel holds when the store runs
-    z = _ints((N, C1, H, H), 11, -3, 3)
-    add = _ints((N, C1, H, H), 12) if act2 else None
+    z = _ints((N, C1, H, W), 11, -3, 3)
+    add = _ints((N, C1, H, W), 12) if act2 else None
     scale = torch.tensor([1.0, 2.0, 0.5, -1.0]).repeat(C1 // 4) if affine else None
     shift = torch.tensor([0.0, 1.0, -1.0, 2.0, -2.0, 0.5, 3.0, -0.5]).repeat(C1 // 8) if affine else None
     mean = torch.tensor([1.0, -1.0, 0.0, 2.0]).repeat(C1 // 4)
@@ -314,22 +462,24 @@ def test_fused_producer_backward_bit_exact(pai, cfg):
     du = sel(g, act1) + (sel(add, act2) if add is not None else 0.0)
     du_bf = du.bfloat16().float()
 
-    d = ops.make_desc(dt, tr, N, H, H, C1, C2, Cout, 2, 0, 0, ops.ACT_NONE)
+    d = ops.make_desc(dt, tr, N, H, W, C1, C2, Cout, 2, 0, 0, ops.ACT_NONE)
     ops.ensure_workspace(max(ops.conv_workspace_bytes(d, 0), ops.conv_workspace_bytes(d, 1)), dev())
     wm = fwd_pack(w, bool(tr))
     wd = torch.empty(wm.numel(), dtype=dt, device=dev())
     ops.pack_weights(dt, wm, Cout, 16, Cin, None, wd)
-    dx1 = torch.empty(N * H * H * C1, dtype=dt, device=dev())
-    dx2 = torch.empty(N * H * H * C2, dtype=dt, device=dev()) if C2 else None
+    dx1 = torch.empty(N * H * W * C1, dtype=dt, device=dev())
+    dx2 = torch.empty(N * H * W * C2, dtype=dt, device=dev()) if C2 else None
     part = torch.full((ops.conv_dgrad_bn_rows_max(d) * 2 * C1,), float("nan"), device=dev())
     f = lambda t: None if t is None else t.to(dev())
-    rows = ops.conv_dgrad_bn(d, nhwc(dy, dt), wd, dx1, dx2, nhwc(z, dt), act1, nhwc(add, dt) if add is not None else None, act2,
-                             f(scale), f(shift), f(mean), f(rstd), part)
-    torch.cuda.synchronize()
-    assert ops.conv_kernel_id(d, 1) in (2, 3) and rows > 0                  # the matrix-core kernels: the store IS fused
-    assert torch.equal(from_nhwc(dx1, N, H, H, C1), du_bf), (name, "du")
+    with _pinned(ops, name) as pin:
+        pin.check(d, 1)
+        rows = ops.conv_dgrad_bn(d, nhwc(dy, dt), wd, dx1, dx2, nhwc(z, dt), act1, nhwc(add, dt) if add is not None else None, act2,
+                                 f(scale), f(shift), f(mean), f(rstd), part)
+        torch.cuda.synchronize()
+        assert ops.conv_kernel_id(d, 1) in (2, 3) and rows > 0              # the matrix-core kernels: the store IS fused
+    _same(from_nhwc(dx1, N, H, W, C1), du_bf, name, "du")
     if C2:
-        assert torch.equal(from_nhwc(dx2, N, H, H, C2), x.grad[:, C1:].bfloat16().float()), (name, "skip half")
+        _same(from_nhwc(dx2, N, H, W, C2), x.grad[:, C1:].bfloat16().float(), name, "skip half")
     P = part[: rows * 2 * C1].view(rows, 2, C1).double().sum(0).cpu()
     s1 = du_bf.double().sum((0, 2, 3))
     s2 = (du_bf.double() * ((z.double() - mean.view(1, -1, 1, 1).double()) * rstd.view(1, -1, 1, 1).double())).sum((0, 2, 3))
@@ -340,19 +490,22 @@ def test_fused_producer_backward_bit_exact(pai, cfg):
         assert float((P[1] - s2).abs().max()) <= 1e-5 * float((du_bf.abs() * 8).double().sum((0, 2, 3)).max())
 
 
-@pytest.mark.parametrize("name", ["enc_patch256", "dec_patch256", "enc_splitk"])
+@pytest.mark.parametrize("name", ["enc_patch256", "dec_patch256", "enc_splitk",
+                                  "conv_wide", "convT_tall", "conv_w96", "conv_4rows", "conv_rows8", "conv_untiled",
+                                  "bnT_wide", "bn_tall", "bnT_6x4"])
 def test_relu_epilogue_of_minus_infinity_is_zero(pai, name):
     """The forward epilogue's activation (y_act = act(conv + bias)) on a -inf pre-activation: aten's relu gives 0 and
     LeakyReLU -inf; the branch-free form v > 0 ? v : v x slope would make the ReLU a NaN (checked on the chip with
     scripts/micro/inf_probe.hip).  One +inf input pixel under negative weights puts -inf into every output it reaches."""
     from thesis_pai_reconstruction_amd import ops
-    case = next(c for c in CASES if c[0] == name)
+    case = _case(name)
     _, tr, N, H, C1, C2, Cout, relu, _ = case
+    H, W = _hw(H)
     Cin, dt = C1 + C2, torch.bfloat16
-    OH = H * 2 if tr else H // 2
+    OH, OW = _out_hw(tr, H, W)
     w = _ints((Cin, Cout, 4, 4) if tr else (Cout, Cin, 4, 4), 3, -2, -1)
-    x = _ints((N, Cin, H, H), 1, 0, 1)
-    x[0, 0, H // 2, H // 2] = float("inf")
+    x = _ints((N, Cin, H, W), 1, 0, 1)
+    x[0, 0, H // 2, W // 2] = float("inf")
     x[1, 0, 1, 2] = float("nan")                       # and a NaN stays a NaN through both activations (aten)
     bias = _ints((Cout,), 7, -3, 3)
     pre = F.conv_transpose2d(x, w, bias, stride=2, padding=1) if tr else F.conv2d(x, w, bias, stride=2, padding=1)
@@ -363,56 +516,63 @@ def test_relu_epilogue_of_minus_infinity_is_zero(pai, name):
     X1 = nhwc(x[:, :C1], dt)
     X2 = nhwc(x[:, C1:], dt) if C2 else None
     for act, fn in ((ops.ACT_RELU, F.relu), (ops.ACT_LRELU, lambda v: F.leaky_relu(v, 0.2))):
-        d = ops.make_desc(dt, tr, N, H, H, C1, C2, Cout, 2, 0, 0, act)
+        d = ops.make_desc(dt, tr, N, H, W, C1, C2, Cout, 2, 0, 0, act)
         ops.ensure_workspace(max(ops.conv_workspace_bytes(d, 0), ops.conv_workspace_bytes(d, 1)), dev())
-        ya = torch.empty(N * OH * OH * Cout, dtype=dt, device=dev())
-        ops.conv_fwd(d, X1, X2, wf, bias.to(dev()), y_act=ya)
-        torch.cuda.synchronize()
-        got, want = from_nhwc(ya, N, OH, OH, Cout), fn(pre).bfloat16().float()
+        ya = torch.empty(N * OH * OW * Cout, dtype=dt, device=dev())
+        with _pinned(ops, name) as pin:
+            pin.check(d, 0)
+            ops.conv_fwd(d, X1, X2, wf, bias.to(dev()), y_act=ya)
+            torch.cuda.synchronize()
+        got, want = from_nhwc(ya, N, OH, OW, Cout), fn(pre).bfloat16().float()
         assert torch.equal(torch.isnan(got), torch.isnan(want)), (name, act, int(torch.isnan(got).sum()), int(torch.isnan(want).sum()))
-        assert torch.equal(torch.nan_to_num(got, nan=7.0), torch.nan_to_num(want, nan=7.0)), (name, act)
+        assert torch.equal(torch.nan_to_num(got, nan=7.0), torch.nan_to_num(want, nan=7.0)), (name, act, _first_diff(got, want))
 
 
-@pytest.mark.parametrize("name", ["dec_patch256", "dec_splitk"])
+@pytest.mark.parametrize("name", ["dec_patch256", "dec_splitk",
+                                  "convT_wide", "conv_tall", "convT_h24", "conv_4rows", "convT_rows8", "convT_untiled",
+                                  "bnT_wide", "bnT_tall", "bnT_6x4"])
 def test_infinite_gradient_behind_a_relu_producer_is_zero(pai, name):
     """threshold_backward (the ReLU backward aten runs for reference models/pix2pix.py:99-106) SELECTS: an infinite gradient
     at a position whose pre-activation is <= 0 gives 0, not inf x 0 = NaN.  The fused store computes the negative side as
     g x slope for LeakyReLU; for ReLU it must select a literal zero.  One +inf in dy, positive weights (no inf - inf)."""
     from thesis_pai_reconstruction_amd import ops
-    case = next(c for c in CASES if c[0] == name)
+    case = _case(name)
     _, tr, N, H, C1, C2, Cout, relu, _ = case
+    H, W = _hw(H)
     Cin, dt = C1 + C2, torch.bfloat16
-    OH = H * 2 if tr else H // 2
+    OH, OW = _out_hw(tr, H, W)
     w = _ints((Cin, Cout, 4, 4) if tr else (Cout, Cin, 4, 4), 3, 1, 2)
-    dy = torch.zeros(N, Cout, OH, OH)
-    dy[0, 1, OH // 2, OH // 2 + 1] = float("inf")
+    dy = torch.zeros(N, Cout, OH, OW)
+    dy[0, 1, OH // 2, OW // 2 + 1] = float("inf")
     dy[N - 1, 0, 0, 0] = 3.0
-    x = torch.zeros(N, Cin, H, H, requires_grad=True)
+    x = torch.zeros(N, Cin, H, W, requires_grad=True)
     y = F.conv_transpose2d(x, w, None, stride=2, padding=1) if tr else F.conv2d(x, w, None, stride=2, padding=1)
     y.backward(dy)
     g = x.grad[:, :C1]
     assert torch.isinf(g).any() and not torch.isnan(g).any()
-    z = _ints((N, C1, H, H), 11, -3, 3)
+    z = _ints((N, C1, H, W), 11, -3, 3)
     want = torch.where(z > 0, g, torch.zeros_like(g)).bfloat16().float()
     assert torch.isinf(want).any() and (torch.isinf(g) & (z <= 0)).any()
 
-    d = ops.make_desc(dt, tr, N, H, H, C1, C2, Cout, 2, 0, 0, ops.ACT_NONE)
+    d = ops.make_desc(dt, tr, N, H, W, C1, C2, Cout, 2, 0, 0, ops.ACT_NONE)
     ops.ensure_workspace(max(ops.conv_workspace_bytes(d, 0), ops.conv_workspace_bytes(d, 1)), dev())
     wd = torch.empty(w.numel(), dtype=dt, device=dev())
     ops.pack_weights(dt, fwd_pack(w, bool(tr)), Cout, 16, Cin, None, wd)
-    dx1 = torch.empty(N * H * H * C1, dtype=dt, device=dev())
-    dx2 = torch.empty(N * H * H * C2, dtype=dt, device=dev()) if C2 else None
+    dx1 = torch.empty(N * H * W * C1, dtype=dt, device=dev())
+    dx2 = torch.empty(N * H * W * C2, dtype=dt, device=dev()) if C2 else None
     part = torch.empty(ops.conv_dgrad_bn_rows_max(d) * 2 * C1, device=dev())
     mean, rstd = torch.zeros(C1, device=dev()), torch.ones(C1, device=dev())
-    rows = ops.conv_dgrad_bn(d, nhwc(dy, dt), wd, dx1, dx2, nhwc(z, dt), ops.ACT_RELU, None, ops.ACT_NONE, None, None, mean, rstd, part)
-    torch.cuda.synchronize()
+    with _pinned(ops, name) as pin:
+        pin.check(d, 1)
+        rows = ops.conv_dgrad_bn(d, nhwc(dy, dt), wd, dx1, dx2, nhwc(z, dt), ops.ACT_RELU, None, ops.ACT_NONE, None, None, mean, rstd, part)
+        torch.cuda.synchronize()
     assert rows > 0
-    got = from_nhwc(dx1, N, H, H, C1)
+    got = from_nhwc(dx1, N, H, W, C1)
     assert not torch.isnan(got).any(), int(torch.isnan(got).sum())
-    assert torch.equal(got, want), name
+    assert torch.equal(got, want), (name, _first_diff(got, want))
 
 
-@pytest.mark.parametrize("shape", [(64, 128), (3, 16)], ids=["cfg2_dec7", "small"])
+@pytest.mark.parametrize("shape", [(64, 128), (3, 16), (2, (16, 32)), (2, (48, 16))], ids=["cfg2_dec7", "small", "wide", "tall"])
 def test_fused_producer_backward_of_the_thin_head_bit_exact(pai, shape):
     """pai_conv_dgrad_bn on the head (ConvTranspose2d(64|64 -> 1), reference models/pix2pix.py:185-193): the input
     gradient runs on thin_fwd2_k and the first BatchNorm-backward pass of decoders[6] (read without an activation: du is
@@ -421,19 +581,20 @@ def test_fused_producer_backward_of_the_thin_head_bit_exact(pai, shape):
     fusion switched off (tunable thin_bwd = 0) the entry point's two-pass form gives the same du and the same sums."""
     from thesis_pai_reconstruction_amd import ops
     N, H = shape
+    H, W = _hw(H)
     C1 = C2 = 64
     dt = torch.bfloat16
     w = _ints((C1 + C2, 1, 4, 4), 3)
-    dy = _ints((N, 1, 2 * H, 2 * H), 5)
-    x = torch.zeros(N, C1 + C2, H, H, requires_grad=True)
+    dy = _ints((N, 1, 2 * H, 2 * W), 5)
+    x = torch.zeros(N, C1 + C2, H, W, requires_grad=True)
     F.conv_transpose2d(x, w, None, stride=2, padding=1).backward(dy)
     g = x.grad.bfloat16().float()
-    z = _ints((N, C1, H, H), 11, -3, 3)
+    z = _ints((N, C1, H, W), 11, -3, 3)
     mean = torch.tensor([1.0, -1.0, 0.0, 2.0]).repeat(C1 // 4)
     rstd = torch.tensor([0.5, 1.0, 2.0, 0.25]).repeat(C1 // 4)
     s1 = g[:, :C1].double().sum((0, 2, 3))
     s2 = (g[:, :C1].double() * ((z.double() - mean.view(1, -1, 1, 1).double()) * rstd.view(1, -1, 1, 1).double())).sum((0, 2, 3))
-    d = ops.make_desc(dt, 1, N, H, H, C1, C2, 1, 2, 0, 0, ops.ACT_NONE)
+    d = ops.make_desc(dt, 1, N, H, W, C1, C2, 1, 2, 0, 0, ops.ACT_NONE)
     ops.ensure_scratch(ops.scratch_bytes_for([d]), dev())
     wd = torch.empty(w.numel(), dtype=dt, device=dev())
     ops.pack_weights(dt, fwd_pack(w, True), 1, 16, C1 + C2, None, wd)
@@ -441,8 +602,8 @@ def test_fused_producer_backward_of_the_thin_head_bit_exact(pai, shape):
     for fused in (1, 0):
         ops.set_tunable("thin_bwd", fused)
         try:
-            dx1 = torch.empty(N * H * H * C1, dtype=dt, device=dev())
-            dx2 = torch.empty(N * H * H * C2, dtype=dt, device=dev())
+            dx1 = torch.empty(N * H * W * C1, dtype=dt, device=dev())
+            dx2 = torch.empty(N * H * W * C2, dtype=dt, device=dev())
             part = torch.full((ops.conv_dgrad_bn_rows_max(d) * 2 * C1,), float("nan"), device=dev())
             rows = ops.conv_dgrad_bn(d, nhwc(dy, dt), wd, dx1, dx2, nhwc(z, dt), ops.ACT_NONE, None, ops.ACT_NONE, None, None,
                                      f(mean), f(rstd), part)
@@ -451,8 +612,8 @@ def test_fused_producer_backward_of_the_thin_head_bit_exact(pai, shape):
             ops.set_tunable("thin_bwd")
         assert ops.conv_kernel_id(d, 1) == 4 and rows > 0, (fused, rows)
         if fused:
-            assert rows == min((N * H * H + 63) // 64, 4096), rows          # one partial row per workgroup of thin_fwd2_k
-        assert torch.equal(from_nhwc(dx1, N, H, H, C1), g[:, :C1]) and torch.equal(from_nhwc(dx2, N, H, H, C2), g[:, C1:]), fused
+            assert rows == min((N * H * W + 63) // 64, 4096), rows          # one partial row per workgroup of thin_fwd2_k
+        assert torch.equal(from_nhwc(dx1, N, H, W, C1), g[:, :C1]) and torch.equal(from_nhwc(dx2, N, H, W, C2), g[:, C1:]), fused
         P = part[: rows * 2 * C1].view(rows, 2, C1).double().sum(0).cpu()
         assert torch.equal(P[0], s1) and torch.equal(P[1], s2), fused
 
@@ -461,9 +622,15 @@ def test_fused_producer_backward_of_the_thin_head_bit_exact(pai, shape):
 # (name, transposed, N, H, C1, C2, Cout): encoders[0], discriminator block 0 at the 2 x 64 batch of its own phase, and
 # decoders[7] (reference models/pix2pix.py:141-147,185-193, models/wrapper.py:229)
 THIN = [("cfg2_enc0", 0, 64, 256, 1, 0, 64), ("cfg2_D0", 0, 128, 256, 1, 1, 64), ("cfg2_dec7", 1, 64, 128, 64, 64, 1)]
+# H != W (an (H, W) pair): the row decode and the col2im decode by shifts with lsw != lsh, whole 16 x 16 source tiles of
+# thin_up_k with tx != ty, and sides that are no power of two (division decode; 10 x 18 and 10 x 12 sources have no whole
+# tile and take the col2im path)
+THIN_RECT = [("enc0_wide", 0, 2, (32, 64), 1, 0, 64), ("enc0_npot", 0, 3, (24, 40), 1, 0, 64),
+             ("D0_tall", 0, 2, (64, 32), 1, 1, 64), ("D0_npot", 0, 3, (20, 36), 1, 1, 64),
+             ("head_wide", 1, 2, (16, 32), 64, 64, 1), ("head_tall", 1, 2, (48, 16), 64, 64, 1), ("head_npot", 1, 3, (10, 12), 64, 64, 1)]
 
 
-@pytest.mark.parametrize("case", THIN, ids=[c[0] for c in THIN])
+@pytest.mark.parametrize("case", THIN + THIN_RECT, ids=[c[0] for c in THIN + THIN_RECT])
 def test_thin_layers_bit_exact_at_config2_shapes(pai, case):
     """thin_fwd_k, thin_dgrad_gemm_k + thin_col2im_k and thin_wgrad_k on integer data at full size: every partial sum is
     an exact fp32 integer, so forward (+ bias, + LeakyReLU copy), input gradient and weight / bias gradient must equal
@@ -471,17 +638,18 @@ def test_thin_layers_bit_exact_at_config2_shapes(pai, case):
     asserted strictly (4 = thin matrix-core kernels) with the scratch registered."""
     from thesis_pai_reconstruction_amd import ops
     name, tr, N, H, C1, C2, Cout = case
+    H, W = _hw(H)
     Cin, dt = C1 + C2, torch.bfloat16
-    OH = H * 2 if tr else H // 2
-    x1 = _ints((N, C1, H, H), 1)
-    x2 = _ints((N, C2, H, H), 2) if C2 else None
+    OH, OW = _out_hw(tr, H, W)
+    x1 = _ints((N, C1, H, W), 1)
+    x2 = _ints((N, C2, H, W), 2) if C2 else None
     w = _ints((Cin, Cout, 4, 4) if tr else (Cout, Cin, 4, 4), 3)
     bias = _ints((Cout,), 7, -3, 3)
-    dy = _ints((N, Cout, OH, OH), 5)
+    dy = _ints((N, Cout, OH, OW), 5)
     y_ref, dx_ref, dw_ref = _reference(tr, x1, x2, w, dy, 0, bias)
     db_ref = dy.sum((0, 2, 3))
     assert max(float(t.abs().max()) for t in (y_ref, dx_ref, dw_ref, db_ref)) < 2 ** 24
-    d = ops.make_desc(dt, tr, N, H, H, C1, C2, Cout, 2, 0, 0, ops.ACT_LRELU if not tr else ops.ACT_NONE)
+    d = ops.make_desc(dt, tr, N, H, W, C1, C2, Cout, 2, 0, 0, ops.ACT_LRELU if not tr else ops.ACT_NONE)
     ops.ensure_scratch(ops.scratch_bytes_for([d]), dev())
     want_ops = (0, 1, 2) if tr else (0, 2)
     assert all(ops.conv_kernel_id(d, op) == 4 for op in want_ops), [ops.conv_kernel_id(d, op) for op in (0, 1, 2)]
@@ -491,29 +659,29 @@ def test_thin_layers_bit_exact_at_config2_shapes(pai, case):
     ops.pack_weights(dt, wm, Cout, 16, Cin, wf, wd)
     X1, X2, DY, B = nhwc(x1, dt), (nhwc(x2, dt) if C2 else None), nhwc(dy, dt), bias.to(dev())
     if tr:      # decoders[7]: fp32 output (the engine adds tanh; the exact test leaves it out), both source gradients
-        y32 = torch.empty(N * OH * OH * Cout, dtype=torch.float32, device=dev())
+        y32 = torch.empty(N * OH * OW * Cout, dtype=torch.float32, device=dev())
         ops.conv_fwd(d, X1, X2, wf, B, y_f32=y32)
         torch.cuda.synchronize()
-        assert torch.equal(y32.cpu().view(N, OH, OH, Cout).permute(0, 3, 1, 2), y_ref), (name, "forward")
-        dx1 = torch.empty(N * H * H * C1, dtype=dt, device=dev())
-        dx2 = torch.empty(N * H * H * C2, dtype=dt, device=dev())
+        _same(y32.cpu().view(N, OH, OW, Cout).permute(0, 3, 1, 2), y_ref, name, "forward")
+        dx1 = torch.empty(N * H * W * C1, dtype=dt, device=dev())
+        dx2 = torch.empty(N * H * W * C2, dtype=dt, device=dev())
         ops.conv_dgrad(d, DY, wd, dx1, dx2)
         torch.cuda.synchronize()
-        assert torch.equal(from_nhwc(dx1, N, H, H, C1), dx_ref[:, :C1].bfloat16().float()), (name, "dgrad x1")
-        assert torch.equal(from_nhwc(dx2, N, H, H, C2), dx_ref[:, C1:].bfloat16().float()), (name, "dgrad x2")
+        assert torch.equal(from_nhwc(dx1, N, H, W, C1), dx_ref[:, :C1].bfloat16().float()), (name, "dgrad x1")
+        assert torch.equal(from_nhwc(dx2, N, H, W, C2), dx_ref[:, C1:].bfloat16().float()), (name, "dgrad x2")
     else:
-        y = torch.empty(N * OH * OH * Cout, dtype=dt, device=dev())
+        y = torch.empty(N * OH * OW * Cout, dtype=dt, device=dev())
         ya = torch.empty_like(y)
         ops.conv_fwd(d, X1, X2, wf, B, y_raw=y, y_act=ya)
         torch.cuda.synchronize()
-        assert torch.equal(from_nhwc(y, N, OH, OH, Cout), y_ref.bfloat16().float()), (name, "forward")
-        assert torch.equal(from_nhwc(ya, N, OH, OH, Cout), F.leaky_relu(y_ref, 0.2).bfloat16().float()), (name, "forward act")
+        assert torch.equal(from_nhwc(y, N, OH, OW, Cout), y_ref.bfloat16().float()), (name, "forward")
+        assert torch.equal(from_nhwc(ya, N, OH, OW, Cout), F.leaky_relu(y_ref, 0.2).bfloat16().float()), (name, "forward act")
         del y, ya
         if C2:  # discriminator block 0: the gradient w.r.t. the image half only (what the generator phase asks for)
-            dx2 = torch.empty(N * H * H * C2, dtype=dt, device=dev())
+            dx2 = torch.empty(N * H * W * C2, dtype=dt, device=dev())
             ops.conv_dgrad(d, DY, wd, None, dx2, only_c2=True)
             torch.cuda.synchronize()
-            assert torch.equal(from_nhwc(dx2, N, H, H, C2), dx_ref[:, C1:].bfloat16().float()), (name, "dgrad x2")
+            assert torch.equal(from_nhwc(dx2, N, H, W, C2), dx_ref[:, C1:].bfloat16().float()), (name, "dgrad x2")
     dw = torch.zeros(wm.numel(), dtype=torch.float32, device=dev())
     db = torch.zeros(Cout, dtype=torch.float32, device=dev())
     ops.conv_wgrad(d, X1, X2, DY, dw, db)

@@ -25,7 +25,20 @@ CASES = [
     ("cfg2_enc4", 0, 64, 16, 512, 0, 512),      # 64 x 8 x 8 = 4096 rows: the largest layer the finish takes
     ("cfg2_enc6", 0, 64, 4, 512, 0, 512),       # 256 rows
     ("cfg2_dec2", 1, 64, 4, 512, 512, 512),     # 4 x 1024 rows
+    # H != W, as (H, W): the finish reads z / add and writes its partial rows by output-pixel index -- wide, tall and sides
+    # that are no power of two (division decode in the split launches)
+    ("enc_wide", 0, 4, (4, 16), 256, 0, 256),
+    ("enc_tall", 0, 4, (16, 4), 256, 0, 256),
+    ("enc_12x8", 0, 4, (12, 8), 256, 0, 256),
+    ("dec_wide", 1, 4, (2, 8), 256, 256, 256),
+    ("dec_tall", 1, 4, (8, 2), 256, 256, 256),
+    ("dec_6x4", 1, 4, (6, 4), 256, 256, 256),
 ]
+SPLIT = "gg_fwd_mfma_k<128, 128, true, true, 64>"
+
+
+def _hw(side):
+    return (side, side) if isinstance(side, int) else tuple(side)
 
 
 def _ints(shape, seed, lo=-2, hi=2):
@@ -36,8 +49,11 @@ def _ints(shape, seed, lo=-2, hi=2):
 def _setup(pai, case):
     from thesis_pai_reconstruction_amd import ops
     name, tr, N, H, C1, C2, Cout = case
-    d = ops.make_desc(torch.bfloat16, tr, N, H, H, C1, C2, Cout, 2, 0, 0, ops.ACT_NONE)
+    H, W = _hw(H)
+    d = ops.make_desc(torch.bfloat16, tr, N, H, W, C1, C2, Cout, 2, 0, 0, ops.ACT_NONE)
     ops.ensure_workspace(max(ops.conv_workspace_bytes(d, 0), ops.conv_workspace_bytes(d, 1)), dev())
+    if H != W:      # the rectangular rows are here for the split-K launches and their finish
+        assert ops.conv_kernel_name(d, 0) == SPLIT and ops.conv_kernel_name(d, 1) == SPLIT, name
     return ops, d
 
 
@@ -45,11 +61,12 @@ def _setup(pai, case):
 def test_conv_bn_act_forward_fused_finish(pai, case):
     ops, d = _setup(pai, case)
     name, tr, N, H, C1, C2, Cout = case
+    H, W = _hw(H)
     Cin, dt = C1 + C2, torch.bfloat16
-    OH = H * 2 if tr else H // 2
-    M = N * OH * OH
-    x1 = _ints((N, C1, H, H), 1)
-    x2 = _ints((N, C2, H, H), 2) if C2 else None
+    OH, OW = (H * 2, W * 2) if tr else (H // 2, W // 2)
+    M = N * OH * OW
+    x1 = _ints((N, C1, H, W), 1)
+    x2 = _ints((N, C2, H, W), 2) if C2 else None
     w = _ints((Cin, Cout, 4, 4) if tr else (Cout, Cin, 4, 4), 3)
     bias = _ints((Cout,), 7, -3, 3)
     gamma = torch.linspace(0.5, 1.5, Cout)
@@ -82,7 +99,7 @@ def test_conv_bn_act_forward_fused_finish(pai, case):
             ops.conv_fwd_bn(d, X1, X2, wf, bias.to(dev()), z, a, ops.ACT_LRELU, gamma.to(dev()), beta.to(dev()), 1e-5, 0.1, 2,
                             rm, rv, nbt, st[0], st[1], st[2], st[3], stats)
             torch.cuda.synchronize()
-            out[fused] = (from_nhwc(z, N, OH, OH, Cout), from_nhwc(a, N, OH, OH, Cout), [t.cpu() for t in st], rm.cpu(), rv.cpu(), int(nbt))
+            out[fused] = (from_nhwc(z, N, OH, OW, Cout), from_nhwc(a, N, OH, OW, Cout), [t.cpu() for t in st], rm.cpu(), rv.cpu(), int(nbt))
         finally:
             ops.set_tunable("bn_fuse_small")
     for fused, (z, a, st, rm, rv, nbt) in out.items():
@@ -113,15 +130,16 @@ def test_dgrad_with_producer_batchnorm_backward_fused_finish(pai, case, enc_form
     autograd of  y = conv(act(BN(z)))  (+ the skip consumer), and fused against the three-launch path."""
     ops, d = _setup(pai, case)
     name, tr, N, H, C1, C2, Cout = case
+    H, W = _hw(H)
     Cin, dt = C1 + C2, torch.bfloat16
-    OH = H * 2 if tr else H // 2
-    M = N * H * H
+    OH, OW = (H * 2, W * 2) if tr else (H // 2, W // 2)
+    M = N * H * W
     if M > 4096:
         pytest.skip("the producer tensor has more than 4096 rows: not a fused-finish layer")
     w = _ints((Cin, Cout, 4, 4) if tr else (Cout, Cin, 4, 4), 3)
-    dy = _ints((N, Cout, OH, OH), 5)
-    z = _ints((N, C1, H, H), 11, -3, 3)                  # producer's convolution output
-    gskip = _ints((N, C1, H, H), 12) if enc_form else None
+    dy = _ints((N, Cout, OH, OW), 5)
+    z = _ints((N, C1, H, W), 11, -3, 3)                  # producer's convolution output
+    gskip = _ints((N, C1, H, W), 12) if enc_form else None
     gamma = torch.linspace(0.5, 1.5, C1)
     beta = torch.linspace(-0.4, 0.4, C1)
     act1 = ops.ACT_LRELU if enc_form else ops.ACT_RELU
@@ -130,7 +148,7 @@ def test_dgrad_with_producer_batchnorm_backward_fused_finish(pai, case, enc_form
     gr, br = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
     bn = F.batch_norm(zr, None, None, gr, br, True, 0.1, 1e-5)
     x1 = F.leaky_relu(bn, 0.2) if enc_form else F.relu(bn)
-    x = torch.cat([x1, torch.zeros(N, C2, H, H)], 1) if C2 else x1
+    x = torch.cat([x1, torch.zeros(N, C2, H, W)], 1) if C2 else x1
     y = F.conv_transpose2d(x, w, None, stride=2, padding=1) if tr else F.conv2d(x, w, None, stride=2, padding=1)
     loss = (y * dy).sum()
     if enc_form:
@@ -160,8 +178,8 @@ def test_dgrad_with_producer_batchnorm_backward_fused_finish(pai, case, enc_form
                                     ops.ACT_RELU if enc_form else ops.ACT_NONE, f(scale), f(shift), f(mean.float()), f(rstd.float()),
                                     part, f(gamma), sums, dgamma, dbeta, dz)
             torch.cuda.synchronize()
-            res[fused] = (from_nhwc(dz, N, H, H, C1), dgamma.cpu() - 1.0, dbeta.cpu() + 1.0, sums.cpu(),
-                          from_nhwc(dx2, N, H, H, C2) if C2 else None)
+            res[fused] = (from_nhwc(dz, N, H, W, C1), dgamma.cpu() - 1.0, dbeta.cpu() + 1.0, sums.cpu(),
+                          from_nhwc(dx2, N, H, W, C2) if C2 else None)
         finally:
             ops.set_tunable("bn_fuse_small")
     scale_dz = float(zr.grad.abs().max())
@@ -171,7 +189,7 @@ def test_dgrad_with_producer_batchnorm_backward_fused_finish(pai, case, enc_form
         assert torch.allclose(dg, gr.grad, rtol=2e-3, atol=2e-3 * float(gr.grad.abs().max())), (name, fused, "dgamma")
         assert torch.allclose(db, br.grad, rtol=2e-3, atol=2e-3 * float(br.grad.abs().max())), (name, fused, "dbeta")
         if C2:      # the skip half of the input gradient is a plain convolution gradient: exact on integers
-            xg = torch.zeros(N, Cin, H, H, requires_grad=True)
+            xg = torch.zeros(N, Cin, H, W, requires_grad=True)
             yy = F.conv_transpose2d(xg, w, None, stride=2, padding=1) if tr else F.conv2d(xg, w, None, stride=2, padding=1)
             yy.backward(dy)
             assert torch.equal(dx2, xg.grad[:, C1:].bfloat16().float()), (name, fused, "dx2")

@@ -205,6 +205,40 @@ def test_ragged_batch_against_live_oracle(pai):
             assert float((v.cpu().double() - g[k].double()).norm()) <= 1e-4 * max(float(g[k].double().norm()), 1e-3), k
 
 
+@pytest.mark.parametrize("hw", [(64, 96), (96, 64)], ids=["64x96", "96x64"])
+def test_bf16_mode_tracks_fp32_path_on_a_rectangle(pai, hw):
+    """The batch of test_ragged_batch_against_live_oracle (3 x 1 x 64 x 96) and its transpose on the bf16 matrix-core path
+    against the fp32 path of the same weights, under the bounds of test_bf16_mode_tracks_fp32_oracle for the square image:
+    prediction within 3e-2 relative L2, every logged loss / metric of one GAN step within 2 %.  In bf16 the non-square
+    image reaches the patch, tile and thin kernels; the fp32 path (gg_simt) is held to the oracle by the test above."""
+    mults = (1, 2, 2, 4, 4)
+    rng = np.random.default_rng(5)
+    x = torch.from_numpy(rng.random((3, 1, 64, 96), dtype=np.float32) * 2 - 1)
+    t = torch.from_numpy(rng.random((3, 1, 64, 96), dtype=np.float32) * 2 - 1)
+    if hw == (96, 64):
+        x, t = x.transpose(2, 3).contiguous(), t.transpose(2, 3).contiguous()
+    assert tuple(x.shape[2:]) == hw
+    m16, _, _ = build(pai, mults, "gan", 77, dtype=torch.bfloat16)
+    m32, _, _ = build(pai, mults, "gan", 77)
+    batch = (x.to(DEV), t.to(DEV))
+    with torch.no_grad():
+        p16, p32 = m16.unet(batch[0]), m32.unet(batch[0])
+    rel = float((p16 - p32).norm() / p32.norm())
+    print(f"{hw}: prediction relative L2 {rel:.3e}")
+    assert rel < 3e-2
+    for m in (m16, m32):
+        m.logged = {}
+        m.training_step(batch, 0)
+    torch.cuda.synchronize()
+    assert set(m16.logged) == set(m32.logged) and m32.logged
+    for k, v in m32.logged.items():
+        got, want = float(m16.logged[k]), float(v)
+        print(f"{hw}: {k} bf16 {got:.6g} fp32 {want:.6g}")
+        assert abs(got - want) <= 2e-2 * max(1.0, abs(want)), (k, got, want)
+    for k, p in m16.unet.named_parameters():
+        assert torch.isfinite(p).all(), k
+
+
 def test_bf16_mode_tracks_fp32_oracle(pai, golden_dir):
     """bf16 storage / MFMA path: losses and metrics within 2% of the reference fixture,
     per-image SSIM ordering of the prediction preserved."""
