@@ -885,6 +885,45 @@ int pai_film_norm_bwd(int dtype, const void* g, const void* x, int64_t rows, int
                       const float* gamma, const float* beta, const void* emb, int64_t ld, const unsigned char* mask,
                       float keep_scale, int act, void* dx, void* demb, float* dgamma, float* dbeta, float* ws, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Palette training objective (added under ABI 141, no version change; reference models/palette.py:102-140, 214-231, 254-333,
+ * 368-427): the forward noising q(y_t | y_0) and the MSE + variational-bound loss with its gradient into the U-Net output.
+ * Pixels are fp32 [N][P][C] (NHWC; P pixels per sample, C in 1..4) in both precisions; t is an int32 device tensor [N], and
+ * every kernel clamps t[n] to [0, T - 1] before it indexes a table.  Refused before any launch, with the reason in
+ * pai_last_error: a NULL tensor, N <= 0 or N > 65535, P <= 0, C outside 1..4, T <= 0, a tensor that is not 16-byte aligned, a
+ * size past the int64 / grid limits ("too large").
+ * pai_palette_noise: one launch.  gamma[n] = (gammas[t] - gammas_prev[t]) u[n] + gammas_prev[t] (one fma), noise = z * (t > 0)
+ * (the product: -0 where z < 0), y_t = sqrt(gamma) y0 + sqrt(1 - gamma) noise.  gammas, gammas_prev: fp32 [T] on the device;
+ * u: fp32 [N].  16-byte accesses where 4 | P C, element by element otherwise.
+ * pai_palette_objective: model_out [N][P][Co], Co = C or (learn_var) 2 C as eps | var; table: fp32 [T][6] on the device, row t
+ * = (sqrt(1 - gamma), 1 / sqrt(gamma), the coefficients c0, c1 of y0 and y_t in the posterior mean, log(var_lower),
+ * log(var_upper)) -- the scalars of pai_palette_step.  Per element:
+ *     y0hat = clamp((y_t - s1 eps) rs, -1, 1), pm = c0 y0hat + c1 y_t, tm = c0 y0 + c1 y_t, v = (var + 1) / 2 or 0,
+ *     plv = v log_hi + (1 - v) log_lo, tlv = log_lo
+ *     t != 0: term = 0.5 (-1 + (plv - tlv) + exp(tlv - plv) + (tm - pm)^2 exp(-plv))
+ *     t == 0: term = -log-likelihood of y0 under the discretised Gaussian (mean pm, log-scale plv / 2): the tanh approximation
+ *             of the normal CDF, the 1e-12 clamps and the y0 < -0.999 / y0 > 0.999 branches of palette.py:386-427
+ * out (fp32 [3 + N]): out[0] = mean (eps - noise)^2 over N P C, out[3 + n] = vlb_n = mean_p,c term / ln 2, out[1] = mean_n vlb_n,
+ * out[2] = out[0] + vlb_weight out[1] (out[0] itself when vlb_weight == 0).  dout [N][P][Co] = d out[2] / d model_out: the eps
+ * columns 2 (eps - noise) / (N P C) (the bound sees a detached eps), the var columns vlb_weight / (N P C ln 2) dterm/dplv
+ * (log_hi - log_lo) / 2; a log(clamp(q, 1e-12)) passes its gradient where q >= 1e-12.  expf / logf / tanhf in full precision;
+ * -1 + (plv - tlv) + exp(tlv - plv) is formed as x + expm1(-x) with x = v (log_hi - log_lo), and exp(-plv / 2) is capped at
+ * 3e37, so that a variance output far outside [-1, 1] gives a saturated CDF and a zero gradient, not inf * 0.
+ * Two launches.  Launch 1, grid (slabs, N): the workgroup of a (slab, sample) writes its part of dout and its two partial sums
+ * (fp64) to ws; a slab that owns no pixel writes zeros.  Launch 2, one workgroup: the partials summed in fp64 in a fixed
+ * order.  No atomics, no sum in arrival order: the same bits on every run.  16-byte accesses where 4 | P (a thread owns four
+ * consecutive pixels), pixel by pixel otherwise.  ws: pai_palette_objective_ws_floats(N, P) floats, any content.
+ * pai_palette_objective_slabs(P): min(256, ceil(P / 1024)); slab i owns the pixels [i pps, (i + 1) pps) below P, pps =
+ * ceil(P / slabs) rounded up to a multiple of 1024.  Both queries are host only and return 0 for arguments out of range. */
+int pai_palette_noise(const float* y0, const float* z, const float* u, const int32_t* t, const float* gammas,
+                      const float* gammas_prev, int T, int N, int64_t P, int C, float* y_t, float* noise, float* gamma,
+                      void* stream);
+int pai_palette_objective_slabs(int64_t P);
+int64_t pai_palette_objective_ws_floats(int N, int64_t P);
+int pai_palette_objective(const float* model_out, const float* noise, const float* y0, const float* y_t, const int32_t* t,
+                          const float* table, int T, int N, int64_t P, int C, int learn_var, float vlb_weight, float* out,
+                          float* dout, float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,8 +42,9 @@ def main(hparams):
                                  dropout=hparams.dropout, loss_type=hparams.loss_type)
     elif hparams.model == "palette":
         raise NotImplementedError(
-            "model 'palette': training (training_step, the VLB term, the LinearLR schedule, the backward passes) is not "
-            "built; sampling is -- pai.Palette loads a checkpoint and report.py -m palette evaluates it (DESIGN.md 7c)")
+            "model 'palette': training under this Lightning loop is not wired (training_step / configure_optimizers still "
+            "refuse); scripts/train_palette.py trains it through Palette.fit_step, pai.Palette loads the checkpoint and "
+            "report.py -m palette evaluates it (DESIGN.md 7c)")
     else:
         raise ValueError(f"Incorrect model name ({hparams.model})")
 

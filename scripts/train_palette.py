@@ -1,0 +1,103 @@
+"""Train pai.Palette with ``Palette.fit_step`` and write a checkpoint that ``pai.Palette.load_from_checkpoint`` and
+``report.py -m palette`` load.
+
+    python scripts/train_palette.py NAME --synthetic 64 --image-size 64 --steps 100
+    python scripts/train_palette.py NAME -d train.yaml --steps 20000 --precision bf16-mixed
+
+The loop is the one main.py does not have for this model: draw t, noise the target, the train-mode U-Net pass, the MSE +
+variational-bound objective, backward, Adam, LinearLR -- all inside ``fit_step``, which returns the loss as a device scalar.
+The loss is copied to the host only every ``--log-every`` steps.  The checkpoint goes to logs/NAME/palette.ckpt (or ``--out``)
+with the hyper-parameters, the weights, the optimizer and scheduler states and the step count.
+"""
+import argparse
+import os
+import pathlib
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import pai_bootstrap  # noqa: E402
+
+pai = pai_bootstrap.load()
+
+
+def to_tuple(text):
+    return tuple(int(v) for v in str(text).split(",") if v != "")
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("name")
+    p.add_argument("-d", "--data", type=pathlib.Path, help="YAML list of training pairs (dataset.ImageDataModule)")
+    p.add_argument("--synthetic", default=0, type=int, help="train on N synthetic pairs instead")
+    p.add_argument("--image-size", default=256, type=int)
+    p.add_argument("-s", "--steps", default=100, type=int)
+    p.add_argument("--batch-size", default=2, type=int)
+    p.add_argument("--precision", default="32")
+    p.add_argument("--channel-mults", default="1,1,2,2,4,4")
+    p.add_argument("--attention-res", default="16,8")
+    p.add_argument("--dropout", default=0.1, type=float)
+    p.add_argument("--schedule", default="linear", choices=["linear", "cosine"])
+    p.add_argument("--learn-variance", default=False, action=argparse.BooleanOptionalAction)
+    p.add_argument("--inference-steps", default=100, type=int)
+    p.add_argument("--log-every", default=10, type=int)
+    p.add_argument("--seed", default=0, type=int)
+    p.add_argument("--out", type=pathlib.Path, help="checkpoint path (default logs/NAME/palette.ckpt)")
+    return p
+
+
+def main(args):
+    from thesis_pai_reconstruction_amd.dataset import ImageDataModule, SyntheticDataModule
+    if not torch.cuda.is_available():
+        raise pai.PaiError("train_palette needs a HIP device; there is no CPU path")
+    if bool(args.synthetic) == (args.data is not None):
+        raise SystemExit("give either --synthetic N or -d LIST")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    torch.manual_seed(args.seed)
+    model = pai.Palette(in_channels=1, out_channels=1, channel_mults=to_tuple(args.channel_mults),
+                        attention_res=to_tuple(args.attention_res), dropout=args.dropout, schedule_type=args.schedule,
+                        learn_var=args.learn_variance, inference_steps=args.inference_steps).to(dev)
+    model.set_precision(args.precision)
+    model.train()
+    if args.synthetic:
+        data = SyntheticDataModule(n_train=args.synthetic, n_val=args.batch_size, batch_size=args.batch_size, size=args.image_size,
+                                   seed=1234, world=1, rank=0)
+    else:
+        data = ImageDataModule(args.data, None, batch_size=args.batch_size, normalize=True, world=1, rank=0, size=args.image_size)
+    data.setup("fit")
+    loader = data.train_dataloader()
+    (opt,), (sched,) = model.make_optimizers()
+    step, epoch, loss = 0, 0, None
+    while step < args.steps:
+        if hasattr(loader, "set_epoch"):
+            loader.set_epoch(epoch)
+        seen = 0
+        for x, y in loader:
+            seen += 1
+            loss = model.fit_step((x.to(dev), y.to(dev)), opt, sched)
+            step += 1
+            if step % args.log_every == 0 or step == args.steps:
+                print(f"[step {step}] " + " ".join(f"{k}={float(v):.5g}" for k, v in model.logged.items())
+                      + f" lr={opt.param_groups[0]['lr']:.4g}", flush=True)
+            if step >= args.steps:
+                break
+        if not seen:
+            raise SystemExit("the data set gives no batch")
+        epoch += 1
+    out = args.out or pathlib.Path("logs") / args.name / "palette.ckpt"
+    os.makedirs(out.parent, exist_ok=True)
+    tmp = str(out) + ".tmp"
+    torch.save({"epoch": epoch, "global_step": step, "hyper_parameters": model.hparams,
+                "state_dict": {k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()},
+                "optimizer_states": [opt.state_dict()], "lr_schedulers": [sched.state_dict()]}, tmp)
+    os.replace(tmp, str(out))
+    print(f"wrote {out} after {step} steps, loss {float(loss):.5g}", flush=True)
+    return {"checkpoint": str(out), "steps": step, "loss": float(loss)}
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

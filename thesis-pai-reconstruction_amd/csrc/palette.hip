@@ -1,5 +1,6 @@
 // Palette sampling (reference models/palette.py:79-100,233-306 and models/guided_diffusion/unet.py, nn.py): the kernels the
-// eval-mode guided-diffusion U-Net and the reverse step need beside the convolution family, and the attention's backward.
+// eval-mode guided-diffusion U-Net and the reverse step need beside the convolution family, the attention's backward, and the
+// training objective.
 //
 //   pai_sattn_fwd        QKVAttentionLegacy (unet.py:265-297) over the T = H * W tokens of a level, flash style: the T x T
 //                        scores are never stored.  bf16: one workgroup of four waves per 128 queries of one (image, head),
@@ -23,6 +24,10 @@
 //   pai_silu_bwd         du = g SiLU'(u): the two SiLUs of the embedding path (training).
 //   pai_gamma_embedding  [cos(g f_i) | sin(g f_i)] (nn.py:140-157).
 //   pai_palette_step     one reverse diffusion step, elementwise (palette.py:233-306).
+//   pai_palette_noise    the forward noising q(y_t | y_0) with t, gammas and gammas_prev on the device (palette.py:214-231; training).
+//   pai_palette_objective  the MSE + variational-bound loss and its gradient into the U-Net output (palette.py:122-140, 254-333,
+//                        368-427; training): a pass over (slab, sample) workgroups with fp64 partial sums, then one workgroup
+//                        that adds them in a fixed order.
 #include "common.h"
 
 #include <math.h>
@@ -1069,6 +1074,311 @@ extern "C" int pai_palette_step(int dtype, const void* model_out, const float* y
     else
         hipLaunchKernelGGL(palette_step_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)model_out, y_t, noise, numel, C, learn_var,
                            add_noise, s1, rs, c0, c1, log_lo, log_hi, y_next, (bf16_t*)xy_next);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- forward noising q(y_t | y_0) ----------------------------------------------------------------------------------------------------
+// gamma = (gammas[t] - gammas_prev[t]) u + gammas_prev[t], noise = z (t > 0), y_t = sqrt(gamma) y0 + sqrt(1 - gamma) noise
+// (palette.py:214-231).  Grid (chunks, N): sample n reads its t, clamped into the table, once.  VEC: 4 | P C, a thread owns one
+// 16-byte vector of each tensor; otherwise one element.  The thread (0, 0) of a sample writes gamma[n].
+template <bool VEC>
+__global__ __launch_bounds__(256) void palette_noise_k(const float* y0, const float* z, const float* u, const int* t,
+                                                       const float* gammas, const float* gammas_prev, int T, int64_t PC, float* y_t,
+                                                       float* noise, float* gamma) {
+    const int n = blockIdx.y;
+    const int tc = min(max(t[n], 0), T - 1);
+    const float gp = gammas_prev[tc];
+    const float g = fmaf(gammas[tc] - gp, u[n], gp);
+    const float keep = tc > 0 ? 1.f : 0.f;             // the product z * 0 keeps the sign of z, as torch's z * (t > 0)
+    const float sg = sqrtf(g), s1 = sqrtf(1.f - g);
+    if (blockIdx.x == 0 && threadIdx.x == 0) gamma[n] = g;
+    const int64_t base = (int64_t)n * PC;
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
+    if (i >= PC) return;
+    if (VEC) {
+        const float4 a = *(const float4*)(y0 + base + i), b = *(const float4*)(z + base + i);
+        float4 e, y;
+        e.x = b.x * keep, e.y = b.y * keep, e.z = b.z * keep, e.w = b.w * keep;
+        y.x = fmaf(sg, a.x, s1 * e.x), y.y = fmaf(sg, a.y, s1 * e.y), y.z = fmaf(sg, a.z, s1 * e.z), y.w = fmaf(sg, a.w, s1 * e.w);
+        *(float4*)(noise + base + i) = e;
+        *(float4*)(y_t + base + i) = y;
+    } else {
+        const float e = z[base + i] * keep;
+        noise[base + i] = e;
+        y_t[base + i] = fmaf(sg, y0[base + i], s1 * e);
+    }
+}
+
+#define PAI_ALIGNED16(p) (((uintptr_t)(p) & 15) == 0)
+
+extern "C" int pai_palette_noise(const float* y0, const float* z, const float* u, const int32_t* t, const float* gammas,
+                                 const float* gammas_prev, int T, int N, int64_t P, int C, float* y_t, float* noise, float* gamma,
+                                 void* stream) {
+    PAI_CHECK(y0 && z && u && t && gammas && gammas_prev && y_t && noise && gamma, "pai_palette_noise: null tensor");
+    PAI_CHECK(N >= 1 && P >= 1, "pai_palette_noise: N=%d P=%lld", N, (long long)P);
+    PAI_CHECK(C >= 1 && C <= 4, "pai_palette_noise: C=%d (1..4)", C);
+    PAI_CHECK(T >= 1, "pai_palette_noise: T=%d", T);
+    PAI_CHECK(PAI_ALIGNED16(y0) && PAI_ALIGNED16(z) && PAI_ALIGNED16(u) && PAI_ALIGNED16(t) && PAI_ALIGNED16(gammas) &&
+                  PAI_ALIGNED16(gammas_prev) && PAI_ALIGNED16(y_t) && PAI_ALIGNED16(noise) && PAI_ALIGNED16(gamma),
+              "pai_palette_noise: tensors must be 16-byte aligned");
+    PAI_CHECK(N <= 65535 && P <= (1ll << 40), "pai_palette_noise: tensor too large (N=%d P=%lld)", N, (long long)P);
+    const int64_t PC = P * C;
+    const bool vec = PC % 4 == 0;
+    const int64_t chunks = ((vec ? PC / 4 : PC) + 255) / 256;
+    PAI_CHECK(chunks < (1ll << 31) && PC <= (1ll << 62) / N, "pai_palette_noise: tensor too large");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)chunks, (unsigned)N);
+    if (vec)
+        hipLaunchKernelGGL(palette_noise_k<true>, grid, dim3(256), 0, s, y0, z, u, t, gammas, gammas_prev, T, PC, y_t, noise, gamma);
+    else
+        hipLaunchKernelGGL(palette_noise_k<false>, grid, dim3(256), 0, s, y0, z, u, t, gammas, gammas_prev, T, PC, y_t, noise, gamma);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- MSE + variational bound and the gradient into the U-Net output -----------------------------------------------------------
+// The formulas of pai_hip.h (palette.py:254-333, 368-427).  Everything per element is fp32 with expf / logf / tanhf (the KL term
+// cancels to 1e-18 at large t and exp(-plv) reaches 1e10 at t = 0: no fast intrinsics); the sums leave the thread as fp64.
+struct PaletteRow {
+    float s1, rs, c0, c1, log_lo, log_hi;
+};
+
+// Phi(a), the tanh approximation of the normal CDF, and phi = dPhi / da
+__device__ __forceinline__ void palette_cdf(float a, float& cdf, float& pdf) {
+    const float k = 0.7978845608028654f;              // sqrt(2 / pi)
+    const float th = tanhf(k * (a + 0.044715f * (a * a * a)));
+    const float s = 1.f - th * th;
+    cdf = 0.5f * (1.f + th);
+    pdf = s == 0.f ? 0.f : 0.5f * s * (k * (1.f + 3.f * 0.044715f * (a * a)));      // a saturated tanh: 0, not 0 * inf
+}
+
+// One element: returns term, and dterm / dplv in `dplv` (LV only).  nll is uniform over the workgroup.
+template <bool LV>
+__device__ __forceinline__ float palette_term(const PaletteRow& r, bool nll, float eps, float var, float y0, float yt, float& dplv) {
+    float y0hat = r.rs * fmaf(-r.s1, eps, yt);
+    y0hat = fminf(fmaxf(y0hat, -1.f), 1.f);
+    const float pm = r.c0 * y0hat + r.c1 * yt;
+    float plv = r.log_lo, x = 0.f;                     // x = plv - tlv = v (log_hi - log_lo), formed without the two large logs
+    if (LV) {
+        const float v = (var + 1.f) * 0.5f;
+        plv = v * r.log_hi + (1.f - v) * r.log_lo;
+        x = v * (r.log_hi - r.log_lo);
+    }
+    if (!nll) {
+        // -1 + x + exp(-x) as x + expm1(-x): at large t x is 1e-3 and the sum of the three would keep only the rounding of 1
+        const float tm = r.c0 * y0 + r.c1 * yt;
+        const float d = tm - pm, em = expm1f(-x), e2 = d == 0.f ? 0.f : (d * d) * expf(-plv);
+        dplv = 0.5f * (-em - e2);
+        return 0.5f * ((x + em) + e2);
+    }
+    // 1 / stddev, kept finite: a variance output far outside [-1, 1] takes exp past the fp32 range, and inf * 0 would be a NaN
+    // where exact arithmetic has a saturated CDF
+    const float inv = fminf(expf(-0.5f * plv), 3e37f), cx = y0 - pm;
+    const float ap = inv * (cx + 1.f / 255.f), am = inv * (cx - 1.f / 255.f);
+    float cp, pp, cm, pmn;
+    palette_cdf(ap, cp, pp);
+    palette_cdf(am, cm, pmn);
+    float q, num;                                      // L = log(max(q, 1e-12)), dL/dls = num / q where q >= 1e-12
+    if (y0 < -0.999f) {
+        q = cp, num = -ap * pp;
+    } else if (y0 > 0.999f) {
+        q = 1.f - cm, num = am * pmn;
+    } else {
+        q = cp - cm, num = am * pmn - ap * pp;
+    }
+    const bool pass = q >= 1e-12f;
+    dplv = pass ? -0.5f * (num / q) : 0.f;
+    return -logf(pass ? q : 1e-12f);
+}
+
+__device__ __forceinline__ PaletteRow palette_row(const float* table, const int* t, int n, int T, bool& nll) {
+    const int tc = min(max(t[n], 0), T - 1);
+    const float* row = table + (int64_t)tc * 6;
+    nll = tc == 0;
+    return PaletteRow{row[0], row[1], row[2], row[3], row[4], row[5]};
+}
+
+// The two sums of a workgroup, in a fixed order: lanes by xor shuffles, the four waves by thread 0.
+__device__ __forceinline__ void palette_block_sums(float se, float tm, double* dst) {
+    __shared__ double red[2][4];
+    double a = (double)se, b = (double)tm;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = a, red[1][threadIdx.x >> 6] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        dst[0] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+        dst[1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+    }
+}
+
+// 4 | P: a thread owns four consecutive pixels, C 16-byte vectors of each pixel tensor and Co of model_out / dout.
+template <int C, bool LV>
+__global__ __launch_bounds__(256) void palette_objective_vec_k(const float* mo, const float* noise, const float* y0, const float* y_t,
+                                                               const int* t, const float* table, int T, int64_t P, int64_t pps,
+                                                               float ge_scale, float gv_scale, float* dout, double* ws) {
+    constexpr int Co = LV ? 2 * C : C;
+    const int n = blockIdx.y;
+    bool nll;
+    const PaletteRow r = palette_row(table, t, n, T, nll);
+    const float gv = gv_scale * (r.log_hi - r.log_lo);
+    const int64_t p0 = (int64_t)blockIdx.x * pps, p1 = min(P, p0 + pps);
+    float se = 0.f, tm = 0.f;
+    for (int64_t p = p0 + threadIdx.x * 4; p < p1; p += 1024) {
+        const int64_t px = (int64_t)n * P + p;
+        alignas(16) float m[4 * Co], e[4 * C], a[4 * C], y[4 * C];
+#pragma unroll
+        for (int v = 0; v < Co; ++v) *(float4*)(m + 4 * v) = *(const float4*)(mo + px * Co + 4 * v);
+#pragma unroll
+        for (int v = 0; v < C; ++v) {
+            *(float4*)(e + 4 * v) = *(const float4*)(noise + px * C + 4 * v);
+            *(float4*)(a + 4 * v) = *(const float4*)(y0 + px * C + 4 * v);
+            *(float4*)(y + 4 * v) = *(const float4*)(y_t + px * C + 4 * v);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float eps = m[k * Co + c], d = eps - e[k * C + c];
+                float dplv = 0.f;
+                tm += palette_term<LV>(r, nll, eps, LV ? m[k * Co + C + c] : 0.f, a[k * C + c], y[k * C + c], dplv);
+                se += d * d;
+                m[k * Co + c] = ge_scale * d;
+                if (LV) m[k * Co + C + c] = gv * dplv;
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < Co; ++v) *(float4*)(dout + px * Co + 4 * v) = *(const float4*)(m + 4 * v);
+    }
+    palette_block_sums(se, tm, ws + 2 * ((int64_t)n * gridDim.x + blockIdx.x));
+}
+
+// any P: a thread owns one pixel at a time
+template <bool LV>
+__global__ __launch_bounds__(256) void palette_objective_px_k(const float* mo, const float* noise, const float* y0, const float* y_t,
+                                                              const int* t, const float* table, int T, int64_t P, int64_t pps, int C,
+                                                              float ge_scale, float gv_scale, float* dout, double* ws) {
+    const int Co = LV ? 2 * C : C;
+    const int n = blockIdx.y;
+    bool nll;
+    const PaletteRow r = palette_row(table, t, n, T, nll);
+    const float gv = gv_scale * (r.log_hi - r.log_lo);
+    const int64_t p0 = (int64_t)blockIdx.x * pps, p1 = min(P, p0 + pps);
+    float se = 0.f, tm = 0.f;
+    for (int64_t p = p0 + threadIdx.x; p < p1; p += 256) {
+        const int64_t px = (int64_t)n * P + p;
+        for (int c = 0; c < C; ++c) {
+            const float eps = mo[px * Co + c], d = eps - noise[px * C + c];
+            float dplv = 0.f;
+            tm += palette_term<LV>(r, nll, eps, LV ? mo[px * Co + C + c] : 0.f, y0[px * C + c], y_t[px * C + c], dplv);
+            se += d * d;
+            dout[px * Co + c] = ge_scale * d;
+            if (LV) dout[px * Co + C + c] = gv * dplv;
+        }
+    }
+    palette_block_sums(se, tm, ws + 2 * ((int64_t)n * gridDim.x + blockIdx.x));
+}
+
+// One workgroup: sample n = thread, thread + 256, ... adds its slabs in order; the samples of a thread in order; then a tree over
+// the 256 threads in LDS.  out[0] = mse, out[1] = mean vlb_n, out[2] = the loss, out[3 + n] = vlb_n.
+__global__ __launch_bounds__(256) void palette_objective_fin_k(const double* ws, int N, int slabs, double inv_npc, double inv_pc_ln2,
+                                                               float vlb_weight, float* out) {
+    __shared__ double red[2][256];
+    double se = 0.0, vl = 0.0;
+    for (int n = threadIdx.x; n < N; n += 256) {
+        double a = 0.0, b = 0.0;
+        for (int s = 0; s < slabs; ++s) {
+            a += ws[2 * ((int64_t)n * slabs + s)];
+            b += ws[2 * ((int64_t)n * slabs + s) + 1];
+        }
+        const double v = b * inv_pc_ln2;
+        out[3 + n] = (float)v;
+        se += a;
+        vl += v;
+    }
+    red[0][threadIdx.x] = se, red[1][threadIdx.x] = vl;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + o];
+            red[1][threadIdx.x] += red[1][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double mse = red[0][0] * inv_npc, vlb = red[1][0] / (double)N;
+        out[0] = (float)mse;
+        out[1] = (float)vlb;
+        out[2] = vlb_weight == 0.f ? (float)mse : (float)(mse + (double)vlb_weight * vlb);
+    }
+}
+
+extern "C" int pai_palette_objective_slabs(int64_t P) {
+    if (P < 1 || P > (1ll << 40)) return 0;
+    const int64_t s = (P + 1023) / 1024;
+    return (int)(s < 256 ? s : 256);
+}
+
+static int64_t palette_objective_pps(int64_t P) {
+    const int64_t slabs = pai_palette_objective_slabs(P);
+    return ((P + slabs - 1) / slabs + 1023) / 1024 * 1024;
+}
+
+extern "C" int64_t pai_palette_objective_ws_floats(int N, int64_t P) {
+    const int slabs = pai_palette_objective_slabs(P);
+    if (N < 1 || N > 65535 || slabs == 0) return 0;
+    return 4 * (int64_t)N * slabs;                     // two fp64 partial sums per (sample, slab)
+}
+
+extern "C" int pai_palette_objective(const float* model_out, const float* noise, const float* y0, const float* y_t, const int32_t* t,
+                                     const float* table, int T, int N, int64_t P, int C, int learn_var, float vlb_weight, float* out,
+                                     float* dout, float* ws, void* stream) {
+    PAI_CHECK(model_out && noise && y0 && y_t && t && table && out && dout && ws, "pai_palette_objective: null tensor");
+    PAI_CHECK(N >= 1 && P >= 1, "pai_palette_objective: N=%d P=%lld", N, (long long)P);
+    PAI_CHECK(C >= 1 && C <= 4, "pai_palette_objective: C=%d (1..4)", C);
+    PAI_CHECK(T >= 1, "pai_palette_objective: T=%d", T);
+    PAI_CHECK(PAI_ALIGNED16(model_out) && PAI_ALIGNED16(noise) && PAI_ALIGNED16(y0) && PAI_ALIGNED16(y_t) && PAI_ALIGNED16(t) &&
+                  PAI_ALIGNED16(table) && PAI_ALIGNED16(out) && PAI_ALIGNED16(dout) && PAI_ALIGNED16(ws),
+              "pai_palette_objective: tensors must be 16-byte aligned");
+    PAI_CHECK(N <= 65535 && P <= (1ll << 40), "pai_palette_objective: tensor too large (N=%d P=%lld)", N, (long long)P);
+    const int slabs = pai_palette_objective_slabs(P);
+    const int64_t pps = palette_objective_pps(P);
+    const double npc = (double)N * (double)P * (double)C;
+    const float ge = (float)(2.0 / npc), gvs = (float)((double)vlb_weight * 0.5 / (npc * 0.6931471805599453));
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)slabs, (unsigned)N);
+    double* w = (double*)ws;
+#define PAI_POBJ_VEC(CC)                                                                                                          \
+    case CC:                                                                                                                      \
+        if (learn_var)                                                                                                            \
+            hipLaunchKernelGGL((palette_objective_vec_k<CC, true>), grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, \
+                               pps, ge, gvs, dout, w);                                                                            \
+        else                                                                                                                      \
+            hipLaunchKernelGGL((palette_objective_vec_k<CC, false>), grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, \
+                               pps, ge, gvs, dout, w);                                                                            \
+        break;
+    if (P % 4 == 0) {
+        switch (C) {
+            PAI_POBJ_VEC(1)
+            PAI_POBJ_VEC(2)
+            PAI_POBJ_VEC(3)
+            PAI_POBJ_VEC(4)
+        }
+    } else if (learn_var) {
+        hipLaunchKernelGGL(palette_objective_px_k<true>, grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, pps, C, ge,
+                           gvs, dout, w);
+    } else {
+        hipLaunchKernelGGL(palette_objective_px_k<false>, grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, pps, C, ge,
+                           gvs, dout, w);
+    }
+#undef PAI_POBJ_VEC
+    PAI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(palette_objective_fin_k, dim3(1), dim3(256), 0, s, (const double*)w, N, slabs, 1.0 / npc,
+                       1.0 / ((double)P * (double)C * 0.6931471805599453), vlb_weight, out);
     PAI_LAUNCH_CHECK();
     return 0;
 }

@@ -743,3 +743,105 @@ def film_norm_act(x, weight, bias, emb_out=None, *, act="silu", dropout_mask=Non
     return _FilmNormAct.apply(x, weight, bias, emb_out, dropout_mask, keep_scale, ops.ACT_SILU if act == "silu" else ops.ACT_NONE,
                               running_mean, running_var, num_batches_tracked, float(momentum), float(eps),
                               bool(advance_in_backward))
+
+
+# --------------------------------------------------------------------------------------
+# Palette training objective: forward noising, MSE + variational bound (differentiable)
+# --------------------------------------------------------------------------------------
+def _nhwc_pixels(x, what):
+    """The NHWC memory [N, H, W, C] behind an NCHW fp32 device tensor: the view itself where the memory already is NHWC (what
+    ``UNet.forward_train`` returns, and any single-channel tensor), a copy otherwise."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ops.PaiError(f"{what} needs HIP device tensors (no CPU fallback exists)")
+    if x.dim() != 4 or x.numel() == 0 or x.dtype != torch.float32:
+        raise ops.PaiError(f"{what}: an fp32 [N, C, H, W] tensor is expected, got {x.dtype} {tuple(x.shape)}")
+    return x.permute(0, 2, 3, 1).contiguous()          # no copy when the permuted view is contiguous already
+
+
+def _nchw_view(p):
+    n, h, w, c = p.shape
+    return p.reshape(n, 1, h, w) if c == 1 else p.permute(0, 3, 1, 2)
+
+
+def _steps_i32(t, n, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ops.PaiError(f"{what} needs HIP device tensors (no CPU fallback exists)")
+    if t.numel() != n or t.dtype not in (torch.int32, torch.int64):
+        raise ops.PaiError(f"{what}: t must hold one int32 / int64 step per sample")
+    return t.reshape(-1).to(torch.int32).contiguous()
+
+
+def palette_noise(y0, t, u, z, diffusion):
+    """q(y_t | y_0) of reference models/palette.py:214-231 with the draws handed in: y0, z fp32 [N, C, H, W], t int [N], u fp32
+    [N] (any shape of N elements) on the device -> (y_t, noise, gamma).  gamma = (gammas[t] - gammas_prev[t]) u + gammas_prev[t],
+    noise = z * (t > 0), y_t = sqrt(gamma) y0 + sqrt(1 - gamma) noise in one launch (``pai_palette_noise``); t is clamped to the
+    schedule inside the kernel and never read on the host.  y_t and noise are NCHW views of NHWC memory."""
+    p0 = _nhwc_pixels(y0, "palette_noise")
+    pz = _nhwc_pixels(z, "palette_noise")
+    if pz.shape != p0.shape:
+        raise ops.PaiError("palette_noise: y0 and z differ in shape")
+    n, h, w, c = p0.shape
+    if not 1 <= c <= 4:
+        raise ops.PaiError(f"palette_noise: C={c} (1..4)")
+    ti = _steps_i32(t, n, "palette_noise")
+    if not isinstance(u, torch.Tensor) or not u.is_cuda or u.numel() != n or u.dtype != torch.float32:
+        raise ops.PaiError("palette_noise: u must be an fp32 device tensor of N elements")
+    g, gp = diffusion.gammas, diffusion.gammas_prev
+    if not g.is_cuda or g.device != p0.device:
+        raise ops.PaiError("palette_noise: the schedule buffers are not on the device of y0 (move the model there)")
+    y_t, noise = torch.empty_like(p0), torch.empty_like(p0)
+    gamma = torch.empty(n, dtype=torch.float32, device=p0.device)
+    ops.palette_noise(p0, pz, u.reshape(-1).contiguous(), ti, g.contiguous(), gp.contiguous(), n, h * w, c, y_t, noise, gamma)
+    return _nchw_view(y_t), _nchw_view(noise), gamma
+
+
+class _PaletteObjective(torch.autograd.Function):
+    """(loss, mse, vlb, vlb_n) from ``pai_palette_objective``; the launch that forms the loss also writes d loss / d model_out,
+    which the backward multiplies by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, model_out, noise, y0, y_t, t, table, learn_var):
+        pm = _nhwc_pixels(model_out, "palette_objective")
+        n, h, w, co = pm.shape
+        c = co // 2 if learn_var else co
+        f32 = dict(dtype=torch.float32, device=pm.device)
+        out = torch.empty(3 + n, **f32)
+        dout = torch.empty_like(pm)
+        ws = torch.empty(ops.palette_objective_ws_floats(n, h * w), **f32)
+        ops.palette_objective(pm, noise, y0, y_t, t, table, n, h * w, c, learn_var, 0.001 if learn_var else 0.0, out, dout, ws)
+        ctx.save_for_backward(dout)
+        loss, mse, vlb, vlb_n = out[2].clone(), out[0].clone(), out[1].clone(), out[3:].clone()
+        ctx.mark_non_differentiable(mse, vlb, vlb_n)
+        return loss, mse, vlb, vlb_n
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout, *unused):
+        (dout,) = ctx.saved_tensors
+        return (_nchw_view(_scaled(dout, gout)),) + (None,) * 6
+
+
+def palette_objective(model_out, noise, y0, y_t, t, diffusion, learn_var):
+    """The training objective of reference models/palette.py:122-140 on the device: model_out fp32 [N, C, H, W] (or, learn_var,
+    [N, 2 C, H, W] as eps | var; the NCHW view ``UNet.forward_train`` returns is read in place), noise, y0, y_t fp32
+    [N, C, H, W], t int [N] -> (loss, mse, vlb, vlb_n).  mse = mean (eps - noise)^2; vlb_n = the KL term of the variational bound,
+    or at t = 0 the discretised Gaussian negative log-likelihood, per sample in bits; vlb = mean vlb_n; loss = mse + 0.001 vlb with
+    learn_var, else mse.  Only ``loss`` carries a gradient, and only into model_out: the eps columns get the MSE's (the bound
+    sees a detached eps), the var columns the bound's.  The per-step scalars are gathered on the device from
+    ``diffusion.step_table_device``; nothing is copied to the host."""
+    pm = _nhwc_pixels(model_out, "palette_objective")
+    n, h, w, co = pm.shape
+    if learn_var and co % 2:
+        raise ops.PaiError(f"palette_objective: learn_var needs an even channel count, got {co}")
+    c = co // 2 if learn_var else co
+    if not 1 <= c <= 4:
+        raise ops.PaiError(f"palette_objective: C={c} (1..4)")
+    pix = []
+    for name, v in (("noise", noise), ("y0", y0), ("y_t", y_t)):
+        p = _nhwc_pixels(v, "palette_objective")
+        if p.shape != (n, h, w, c):
+            raise ops.PaiError(f"palette_objective: {name} of shape {tuple(v.shape)} for a model output of {tuple(model_out.shape)}")
+        pix.append(p)
+    ti = _steps_i32(t, n, "palette_objective")
+    table = diffusion.step_table_device(pm.device)
+    return _PaletteObjective.apply(model_out, pix[0], pix[1], pix[2], ti, table, bool(learn_var))

@@ -203,6 +203,10 @@ SIGNATURES = {
     "pai_film_norm_ws_floats": (_L, [_I, _L, _I]),
     "pai_film_norm_fwd": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _F, _I, _P, _P]),
     "pai_film_norm_bwd": (_I, [_I, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _F, _I, _P, _P, _P, _P, _P, _P]),
+    "pai_palette_noise": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _P, _P, _P, _P]),
+    "pai_palette_objective_slabs": (_I, [_L]),
+    "pai_palette_objective_ws_floats": (_L, [_I, _L]),
+    "pai_palette_objective": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _F, _P, _P, _P, _P]),
 }
 
 _lib = None

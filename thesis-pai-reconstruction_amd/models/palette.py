@@ -3,8 +3,10 @@
 Same module tree and state-dict keys as the reference (``unet.*``, ``diffusion.{alphas,gammas,gammas_prev}``,
 ``diffusion_inf.*``), so a checkpoint trained by the reference loads.  Built here: ``forward`` (the reverse process of
 ``diffusion_inf``: one eval-mode U-Net call and one ``pai_palette_step`` launch per step) and ``validation_step``.
-Training (``training_step``, the VLB term, the LinearLR schedule, the optimizer loop) is not built; the differentiable
-train-mode pass of the U-Net alone is ``unet.forward_train``.
+Training runs through names of its own beside the refusals: ``training_loss`` (the forward noising, ``unet.forward_train`` and
+the MSE + variational-bound objective, the latter two kernels of csrc/palette.hip), ``make_optimizers`` (the reference's Adam
+and LinearLR values) and ``fit_step``.  ``training_step`` / ``configure_optimizers`` still raise: the Lightning loop of
+main.py is not wired to them; scripts/train_palette.py is the loop.
 
 The sample chain stays fp32 in both precisions, as NHWC pixels; the U-Net reads ``[x | y_t]`` in the storage dtype from
 one tensor whose y half the step kernel rewrites.  The six scalars of each step come from a table built once on the
@@ -56,6 +58,7 @@ class DiffusionModel(nn.Module):
         self.register_buffer("gammas", torch.cumprod(self.alphas, axis=0))
         self.register_buffer("gammas_prev", torch.cat([torch.ones((1,), device=self.gammas.device), self.gammas[:-1]]))
         self._table = None
+        self._table_dev = None
 
     def _versions(self):
         return tuple(b._version for b in (self.alphas, self.gammas, self.gammas_prev))
@@ -65,6 +68,7 @@ class DiffusionModel(nn.Module):
         out = super()._apply(fn, *args, **kwargs)
         if self._table is not None:
             self._table = (self._versions(), self._table[1])
+        self._table_dev = None
         return out
 
     def step_table(self):
@@ -78,6 +82,15 @@ class DiffusionModel(nn.Module):
                     torch.sqrt(a) * (1 - gp) / (1 - g), torch.log(lower), torch.log(1 - a)]
             self._table = (self._versions(), [tuple(float(v) for v in row) for row in torch.stack(cols, 1)])
         return self._table[1]
+
+    def step_table_device(self, device):
+        """``step_table()`` as an fp32 [timesteps][6] tensor on ``device``: uploaded once per value of the buffers, so that the
+        training objective gathers the row of every sample's t on the device."""
+        d = self._table_dev
+        if d is None or d[0] != self._versions() or d[1].device != torch.device(device):
+            t = torch.tensor(self.step_table(), dtype=torch.float32).to(device)
+            d = self._table_dev = (self._versions(), t)
+        return d[1]
 
 
 class Palette(LightningModule):
@@ -151,10 +164,57 @@ class Palette(LightningModule):
         return out
 
     def configure_optimizers(self):
-        raise NotImplementedError("Palette training is not built; sampling only")
+        raise NotImplementedError("Palette under the Lightning loop is sampling only; train with make_optimizers() / fit_step() "
+                                  "(scripts/train_palette.py)")
 
     def training_step(self, batch, batch_idx=0):
-        raise NotImplementedError("Palette training is not built; sampling only")
+        raise NotImplementedError("Palette under the Lightning loop is sampling only; train with training_loss() / fit_step() "
+                                  "(scripts/train_palette.py)")
+
+    # ---- training (reference models/palette.py:102-140) ---------------------------------------------------------------------
+    def training_loss(self, batch, draws=None):
+        """The loss of one batch ``(x, y_0)`` (fp32 [N x C x H x W] on the device), connected by autograd to the U-Net's
+        parameters: t ~ randint(0, timesteps), the forward noising, ``unet.forward_train(x, y_t, gamma)`` and the MSE +
+        variational-bound objective.  ``draws = (t, z, u)`` (int [N], fp32 like y_0, fp32 [N]; device tensors) replaces the three
+        draws -- tests, as ``noise_fn`` for the sampler.  Logs ``mse_loss``, ``vlb_loss`` and ``loss``.  No host synchronisation."""
+        x, y_0 = batch
+        if not self.training or not self.unet.training:
+            raise PaiError("Palette.training_loss runs in train mode: call train() first")
+        if not (torch.is_tensor(x) and torch.is_tensor(y_0) and x.is_cuda and y_0.is_cuda):
+            raise PaiError("Palette (HIP) needs HIP device tensors; there is no CPU path")
+        n, dev = y_0.shape[0], y_0.device
+        if draws is None:
+            t = torch.randint(0, self.diffusion.timesteps, (n,), device=dev)
+            z = torch.randn(y_0.shape, dtype=torch.float32, device=dev)
+            u = torch.rand(n, dtype=torch.float32, device=dev)
+        else:
+            t, z, u = draws
+        y_t, noise, gamma = PF.palette_noise(y_0, t, u, z, self.diffusion)
+        model_out = self.unet.forward_train(x, y_t, gamma)
+        loss, mse, vlb, _ = PF.palette_objective(model_out, noise, y_0, y_t, t, self.diffusion, self.learn_var)
+        self.log("mse_loss", mse, prog_bar=True)
+        self.log("vlb_loss", vlb, prog_bar=True)
+        self.log("loss", loss, prog_bar=True)
+        return loss
+
+    def make_optimizers(self):
+        """The reference's ``configure_optimizers`` values: Adam(lr = 1e-4) on the U-Net, as the fused ``optim.MultiAdam``, and
+        LinearLR over 10000 steps (factor 1/3 -> 1)."""
+        from ..optim import MultiAdam
+        opt = MultiAdam(self.unet.parameters(), lr=1e-4, betas=(0.9, 0.999), eps=1e-8)
+        return [opt], [torch.optim.lr_scheduler.LinearLR(opt, total_iters=10000)]
+
+    def fit_step(self, batch, optimizer, scheduler=None, draws=None):
+        """One optimisation step: zero_grad, ``training_loss``, backward, ``optimizer.step``, ``scheduler.step``.  Returns the
+        loss as a device scalar; after a first (warm-up) step nothing here copies to the host or synchronises."""
+        optimizer.zero_grad(set_to_none=True)
+        loss = self.training_loss(batch, draws)
+        loss.backward()
+        nnops.join_wgrads()
+        optimizer.step()
+        if scheduler is not None:
+            scheduler.step()
+        return loss.detach()
 
     def _epoch_dir(self):
         tr = self.trainer

@@ -1251,3 +1251,35 @@ def film_norm_bwd(dtype, g, x, rows, N, C_, mean, rstd, gamma, beta, emb, ld, ma
                                        _p(beta, torch.float32), _p(emb, dtype), int(ld), _p(mask, torch.uint8),
                                        float(keep_scale), int(act), _p(dx, dtype), _p(demb, dtype), _p(dgamma, torch.float32),
                                        _p(dbeta, torch.float32), _p(ws, torch.float32), _stream()), "pai_film_norm_bwd")
+
+
+# ---- Palette training objective (csrc/palette.hip) ------------------------------------------------------------------------
+def palette_noise(y0, z, u, t, gammas, gammas_prev, N, P, C_, y_t, noise, gamma):
+    """The forward noising on fp32 pixels [N][P][C]: gamma [N], noise = z * (t > 0) and y_t in one launch; ``t`` int32 [N] and
+    the schedule buffers stay on the device (pai_palette_noise)."""
+    f32 = torch.float32
+    if gammas.numel() != gammas_prev.numel():
+        raise PaiError("palette_noise: gammas and gammas_prev differ in size")
+    L.check(L.load().pai_palette_noise(_p(y0, f32), _p(z, f32), _p(u, f32), _p(t, torch.int32), _p(gammas, f32),
+                                       _p(gammas_prev, f32), int(gammas.numel()), int(N), int(P), int(C_), _p(y_t, f32),
+                                       _p(noise, f32), _p(gamma, f32), _stream()), "pai_palette_noise")
+
+
+def palette_objective_slabs(P) -> int:
+    """Slabs the pixels of one sample are split into by ``palette_objective`` (pai_palette_objective_slabs)."""
+    return L.load().pai_palette_objective_slabs(int(P))
+
+
+def palette_objective_ws_floats(N, P) -> int:
+    """fp32 elements of the workspace of ``palette_objective`` (pai_palette_objective_ws_floats)."""
+    return L.load().pai_palette_objective_ws_floats(int(N), int(P))
+
+
+def palette_objective(model_out, noise, y0, y_t, t, table, N, P, C_, learn_var, vlb_weight, out, dout, ws):
+    """out [3 + N] = (mse, mean vlb, loss, vlb_n ...) and dout = d loss / d model_out in two launches; ``table`` fp32 [T][6] on
+    the device, ``ws`` fp32 [palette_objective_ws_floats(N, P)] (pai_palette_objective)."""
+    f32 = torch.float32
+    L.check(L.load().pai_palette_objective(_p(model_out, f32), _p(noise, f32), _p(y0, f32), _p(y_t, f32), _p(t, torch.int32),
+                                           _p(table, f32), int(table.shape[0]), int(N), int(P), int(C_), int(bool(learn_var)),
+                                           float(vlb_weight), _p(out, f32), _p(dout, f32), _p(ws, f32), _stream()),
+            "pai_palette_objective")
