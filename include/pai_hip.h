@@ -72,7 +72,9 @@ const char* pai_last_error(void);
  * 141: ReLU keeps a NaN in the element-wise passes (pai_bn_apply, pai_bn2_add_act, pai_add_act, the one-launch finish of
  * pai_conv_fwd_bn; they stored 0 for it); pai_bn_apply / pai_bn2_add_act refuse a dtype other than PAI_F32 / PAI_BF16 (they
  * ran it as bf16); the train-mode Palette U-Net pass (pai_avgpool2_bwd, pai_silu_bwd: additions, the number the library
- * already reported stays). */
+ * already reported stays).  Also added under 141, no version change: the first layer's weight gradient in the store of the
+ * next layer's input gradient (pai_conv_dgrad_act_wthin, _ok, _slab_bytes, _kernel_name; tunables "dgrad_wthin",
+ * "wthin_slabs") -- ask for the symbol, not for a number. */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -245,6 +247,31 @@ int pai_conv_dgrad_f32add(const pai_conv_desc* d, const void* dy, const void* w_
  * matrix-core kernels apply it in their store, the others run the second pass themselves. */
 int pai_conv_dgrad_act(const pai_conv_desc* d, const void* dy, const void* w_dgrad, void* dx1,
                        void* dx2, const void* a1, int act1, void* stream);
+
+/* pai_conv_dgrad_act of the layer BEHIND a thin first layer together with that first layer's pai_conv_wgrad, for the case
+ * that the first layer's input needs no gradient: the tile
+ *   du = act1'(a1) * conv_backward_input(dy, w) + act2'(a1) * add        (add may be NULL; as pai_conv_dgrad_bn without norm)
+ * is rounded to the storage dtype as pai_conv_dgrad_act would store it, and instead of being stored it is multiplied with the
+ * 4 x 4 windows of the thin inputs it belongs to:
+ *   dw (+)= conv_backward_weight(x1 | x2, du),  dbias (+)= sum over the pixels of du
+ * -- what pai_conv_dgrad_act into a tensor and pai_conv_wgrad(d_thin, x1, x2, that tensor, dw, dbias) leave, without writing
+ * and reading the tensor (64 channels at the layer's largest resolution).  Equal bits whenever every fp32 sum is exact;
+ * otherwise the summation order differs (workgroups add their tiles into S slabs with fp32 atomics, a second launch sums the
+ * slabs in a fixed order).
+ * d: the layer behind (bf16 k4 s2 Conv2d, 64 input channels, one tensor) whose input gradient runs on 8 x 16-pixel patch
+ * tiles; d_thin: the bf16 k4 s2 (1 | 1) -> 64 layer in front of it.  x1, x2 (NULL for one channel): d_thin's inputs, 16-B
+ * aligned.  dw [64][16][C1 + C2] and dbias [64] (or NULL) are fp32; overwrite 0: both are added to, 1: both are written,
+ * 2: dw is written, dbias added to.  slabs: caller-provided fp32 scratch of pai_conv_dgrad_act_wthin_slab_bytes (fewer bytes
+ * mean fewer slabs; the tunable "wthin_slabs", default 128, sets S), cleared by the call.
+ * pai_conv_dgrad_act_wthin_ok answers 1 / 0 on the host: 0 when the caller needs du itself (need_dx), for every other pair
+ * of layers and when the tunable "dgrad_wthin" is 0; the call refuses every pair the predicate refuses for its shape.
+ * pai_conv_dgrad_act_wthin_kernel_name: the symbol of the main launch, as pai_conv_kernel_name. */
+int pai_conv_dgrad_act_wthin_ok(const pai_conv_desc* d, const pai_conv_desc* d_thin, int need_dx);
+int64_t pai_conv_dgrad_act_wthin_slab_bytes(const pai_conv_desc* d, const pai_conv_desc* d_thin);
+int pai_conv_dgrad_act_wthin_kernel_name(const pai_conv_desc* d, const pai_conv_desc* d_thin, char* name, int name_len);
+int pai_conv_dgrad_act_wthin(const pai_conv_desc* d, const void* dy, const void* w_dgrad, const void* a1, int act1,
+                             const void* add, int act2, const pai_conv_desc* d_thin, const void* x1, const void* x2,
+                             float* dw, float* dbias, int overwrite, float* slabs, int64_t slab_bytes, void* stream);
 
 /* pai_conv_dgrad with the backward of the layer that PRODUCED x1 fused into the store of dx1 --
  * the activation in front of this convolution and, optionally, the first pass of the BatchNorm

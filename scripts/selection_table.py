@@ -29,13 +29,17 @@ def _load(name):
     return mod
 
 
+def _desc(L, dtype, tr, k, s, g, N, H, W, C1, C2, Cout, r1, r2):
+    d = L.ConvDesc()
+    d.dtype, d.transposed, d.N, d.H, d.W, d.C1, d.C2, d.Cout = dtype, tr, N, H, W, C1, C2, Cout
+    d.kernel, d.stride, d.pad = {4: (4, s, 1), 3: (3, 1, 1), 1: (1, 1, 0)}[k]
+    d.relu1, d.relu2, d.groups = r1, r2, g
+    return "dt%d tr%d k%ds%d g%d N%d %dx%d C%d+%d->%d relu%d%d" % (dtype, tr, k, s, g, N, H, W, C1, C2, Cout, r1, r2), d
+
+
 def descriptors(L):
-    def desc(dtype, tr, k, s, g, N, H, W, C1, C2, Cout, r1, r2):
-        d = L.ConvDesc()
-        d.dtype, d.transposed, d.N, d.H, d.W, d.C1, d.C2, d.Cout = dtype, tr, N, H, W, C1, C2, Cout
-        d.kernel, d.stride, d.pad = {4: (4, s, 1), 3: (3, 1, 1), 1: (1, 1, 0)}[k]
-        d.relu1, d.relu2, d.groups = r1, r2, g
-        return "dt%d tr%d k%ds%d g%d N%d %dx%d C%d+%d->%d relu%d%d" % (dtype, tr, k, s, g, N, H, W, C1, C2, Cout, r1, r2), d
+    def desc(*a):
+        return _desc(L, *a)
 
     for dtype in (L.BF16, L.F32):
         for tr, k, s, g in KINDS:
@@ -86,12 +90,27 @@ def dump(path, register):
         row["dgrad_bn_rows_max"] = lib.pai_conv_dgrad_bn_rows_max(p)
         row["prologue_ok"] = lib.pai_conv_prologue_ok(p)
         table[key] = row
+    # pai_conv_dgrad_act_wthin takes a PAIR of layers (thin first layer, the layer behind): rows of their own, for a library
+    # that has the entry point
+    if hasattr(lib, "pai_conv_dgrad_act_wthin_ok"):
+        for dtype in (L.BF16, L.F32):
+            for N in (2, 64, 128):
+                for H, W in ((32, 64), (64, 64), (256, 256), (96, 160)):
+                    for T in (1, 2):
+                        d0 = _desc(L, dtype, 0, 4, 2, 0, N, H, W, 1, T - 1, 64, 0, 0)[1]
+                        d1 = _desc(L, dtype, 0, 4, 2, 0, N, H // 2, W // 2, 64, 0, 128, 0, 0)[1]
+                        ok = lib.pai_conv_dgrad_act_wthin_ok(C.byref(d1), C.byref(d0), 0)
+                        named = lib.pai_conv_dgrad_act_wthin_kernel_name(C.byref(d1), C.byref(d0), buf, 96) == 0
+                        table["wthin:%d:%d:%d:%d:%d" % (dtype, N, H, W, T)] = {
+                            "ok": ok, "name": buf.value.decode() if named else None,
+                            "slab_bytes": lib.pai_conv_dgrad_act_wthin_slab_bytes(C.byref(d1), C.byref(d0))}
     text = json.dumps(table, sort_keys=True, indent=0)
     with open(path, "w") as f:
         f.write(text)
-    names = {r["name%d" % op] for r in table.values() for op in (0, 1, 2)} - {None}
-    ids = {r["id%d" % op] for r in table.values() for op in (0, 1)}
-    print(json.dumps({"lib": L.LIB_PATH, "rows": len(table), "invalid": sum(r["id0"] < 0 for r in table.values()),
+    layers = [r for r in table.values() if "id0" in r]
+    names = ({r["name%d" % op] for r in layers for op in (0, 1, 2)} | {r.get("name") for r in table.values()}) - {None}
+    ids = {r["id%d" % op] for r in layers for op in (0, 1)}
+    print(json.dumps({"lib": L.LIB_PATH, "rows": len(table), "invalid": sum(r["id0"] < 0 for r in layers),
                       "names": len(names), "ids_op01": sorted(ids), "sha256": hashlib.sha256(text.encode()).hexdigest()}))
 
 

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .engine import GradArena, UnetEngine, _BNState, _Packs, _bn_forward, to_fwd_pack_
+from .engine import GradArena, UnetEngine, _BNState, _Packs, _bn_forward, to_fwd_pack_, wthin_slabs
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH
 
 
@@ -359,10 +359,20 @@ class AttentionUnetEngine(UnetEngine):
         wgrad(P["enc_desc"][i], S["a"][i - 1], None, dz, self.enc_conv[i], True)
         _, wd = self.enc_packs[i].get(dtype)
 
+        # encoder 0's weight gradient in the store of encoder 1's input gradient, as UnetEngine.backward
+        enc0_fused = ops.conv_dgrad_act_wthin_ok(P["enc_desc"][1], P["enc_desc"][0], False)
+
         def enc_dgrad(i, dz, wd):
             d = P["enc_desc"][i]
             gx = G["gx"][L - 1 - (i - 1)]      # gate of decoder j = L-1-level
+            if i - 1 == 0 and enc0_fused:
+                c0, d0 = self.enc_conv[0], P["enc_desc"][0]
+                ops.conv_dgrad_act_wthin(d, dz, wd, S["z"][0], ACT_LRELU, gx, ACT_NONE, d0, S["x"], None,
+                                         A.seg(c0.weight), A.seg(c0.bias), wthin_slabs(P, d, d0))
+                return 0
             if i - 1 == 0:
+                if G["dz_enc"][0] is None:
+                    G["dz_enc"][0] = torch.empty_like(S["z"][0])
                 return ops.conv_dgrad_bn(d, dz, wd, G["dz_enc"][0], None, S["z"][0], ACT_LRELU, gx, ACT_NONE)
             pst = S["ebn"][i - 1]
             return ops.conv_dgrad_bn(d, dz, wd, G["ga"][i - 1], None, S["z"][i - 1], ACT_LRELU, gx, ACT_NONE,
@@ -380,11 +390,12 @@ class AttentionUnetEngine(UnetEngine):
             _, wd = self.enc_packs[i].get(dtype)
             fused_rows = enc_dgrad(i, dz, wd)
         conv0 = self.enc_conv[0]
-        with torch.cuda.stream(side.fork_tail()):
-            # same selection as the local wgrad(): with in_channels >= 3 encoder 0 is not a thin layer, its segment is NOT
-            # among the cleared small ones (GradArena._small) and must be overwritten on the first pass, not added to
-            c0_in, c0_out = conv0.weight.shape[1], conv0.weight.shape[0]
-            (ops.conv_wgrad_overwrite_w if (fresh and min(c0_in, c0_out) > 2) else ops.conv_wgrad)(
-                P["enc_desc"][0], S["x"], None, G["dz_enc"][0], A.seg(conv0.weight), A.seg(conv0.bias))
+        if not enc0_fused:
+            with torch.cuda.stream(side.fork_tail()):
+                # same selection as the local wgrad(): with in_channels >= 3 encoder 0 is not a thin layer, its segment is NOT
+                # among the cleared small ones (GradArena._small) and must be overwritten on the first pass, not added to
+                c0_in, c0_out = conv0.weight.shape[1], conv0.weight.shape[0]
+                (ops.conv_wgrad_overwrite_w if (fresh and min(c0_in, c0_out) > 2) else ops.conv_wgrad)(
+                    P["enc_desc"][0], S["x"], None, G["dz_enc"][0], A.seg(conv0.weight), A.seg(conv0.bias))
         side.join()
         done(conv0.bias)

@@ -693,6 +693,88 @@ extern "C" int pai_conv_dgrad_act(const pai_conv_desc* d, const void* dy, const 
     return pai_act_bwd(d->dtype, dx1, act1, nullptr, PAI_ACT_NONE, a1, (int64_t)g.N * g.OH * g.OW * g.D1, dx1, stream);
 }
 
+// ---- pai_conv_dgrad_act_wthin: the input gradient of the layer behind a thin first layer, with that layer's weight and bias
+// gradient formed from the tile in the store -- the gradient tensor between the two is never written.  One selection
+// (pick_wthin) answers the predicate, the name, the slab bytes and the launch.
+struct WthinPick {
+    GG g, gt;                   // the input gradient's gather; the thin layer's forward gather
+    FwdPick p;                  // p.mfma: the plan in its weight-gradient store form
+    int T;                      // thin input channels, 1 | 2
+};
+// nullptr: taken (*o is filled); else why not
+static const char* pick_wthin(const pai_conv_desc* d, const pai_conv_desc* dt, WthinPick* o) {
+    if (!d || !dt) return "null descriptor";
+    if (gg_build_dgrad(d, &o->g) || gg_build_fwd(dt, &o->gt)) return "invalid descriptor";
+    const GG &g = o->g, &gt = o->gt;
+    if (d->dtype != PAI_BF16 || dt->dtype != PAI_BF16) return "bf16 storage only";
+    if (d->transposed || dt->transposed || d->kernel != 4 || dt->kernel != 4 || d->stride != 2 || dt->stride != 2)
+        return "both layers are k4 s2 convolutions";
+    if (!thin_wgrad_conv_ok(dt->dtype, gt) || gt.Cout != 64) return "the thin layer is (1 | 1) -> 64 channels";
+    if (g.D1 != 64 || g.D2 != 0 || g.relu1) return "the next layer reads the thin layer's 64 channels, one tensor";
+    if (gt.N != g.N || gt.OH != g.OH || gt.OW != g.OW) return "the thin layer's output is not the next layer's input";
+    FwdArgs a = query_args(g, 1);
+    a.bz = (const void*)1;
+    o->p = pick_fwd(d->dtype, g, a);
+    o->T = gt.C1 + gt.C2;
+    if (o->p.k != FK_MFMA || !fwd_mfma_wthin(&o->p.mfma, o->T)) return "the input gradient does not run on 8 x 16-pixel, 64-channel patch tiles";
+    o->p.name = o->p.mfma.name;
+    return nullptr;
+}
+
+extern "C" int pai_conv_dgrad_act_wthin_ok(const pai_conv_desc* d, const pai_conv_desc* d_thin, int need_dx) {
+    WthinPick w;
+    return !need_dx && pai_tunable("dgrad_wthin", 1) && pick_wthin(d, d_thin, &w) == nullptr ? 1 : 0;
+}
+
+extern "C" int64_t pai_conv_dgrad_act_wthin_slab_bytes(const pai_conv_desc* d, const pai_conv_desc* d_thin) {
+    WthinPick w;
+    if (pick_wthin(d, d_thin, &w)) return -1;
+    int S = pai_tunable("wthin_slabs", 128);
+    S = S < 1 ? 1 : (S > 4096 ? 4096 : S);
+    return (int64_t)S * wthin_slab_floats(w.T) * sizeof(float);
+}
+
+extern "C" int pai_conv_dgrad_act_wthin_kernel_name(const pai_conv_desc* d, const pai_conv_desc* d_thin, char* name, int name_len) {
+    WthinPick w;
+    if (pick_wthin(d, d_thin, &w) || !name || name_len <= 0) return -1;
+    strncpy(name, w.p.name, name_len - 1);
+    name[name_len - 1] = 0;
+    return 0;
+}
+
+extern "C" int pai_conv_dgrad_act_wthin(const pai_conv_desc* d, const void* dy, const void* w_dgrad, const void* a1, int act1,
+                                        const void* add, int act2, const pai_conv_desc* d_thin, const void* x1, const void* x2,
+                                        float* dw, float* dbias, int overwrite, float* slabs, int64_t slab_bytes, void* stream) {
+    WthinPick w;
+    const char* why = pick_wthin(d, d_thin, &w);
+    PAI_CHECK(!why, "pai_conv_dgrad_act_wthin: %s (ask pai_conv_dgrad_act_wthin_ok)", why);
+    PAI_CHECK(dy && w_dgrad && a1 && x1 && dw && slabs, "pai_conv_dgrad_act_wthin: null pointer");
+    PAI_CHECK((w.T == 2) == (x2 != nullptr), "pai_conv_dgrad_act_wthin: x2 goes with the thin layer's second channel");
+    PAI_CHECK(((uintptr_t)x1 & 15) == 0 && ((uintptr_t)x2 & 15) == 0, "pai_conv_dgrad_act_wthin: the thin inputs are read in 16-B chunks");
+    for (int act : {act1, act2})
+        PAI_CHECK(act == PAI_ACT_LRELU || act == PAI_ACT_RELU || act == PAI_ACT_NONE, "pai_conv_dgrad_act_wthin: act=%d", act);
+    PAI_CHECK(overwrite >= 0 && overwrite <= 2, "pai_conv_dgrad_act_wthin: overwrite=%d", overwrite);
+    const int64_t per = (int64_t)wthin_slab_floats(w.T) * sizeof(float);
+    int S = pai_tunable("wthin_slabs", 128);
+    S = S < 1 ? 1 : (S > 4096 ? 4096 : S);
+    if ((int64_t)S * per > slab_bytes) S = (int)(slab_bytes / per);
+    PAI_CHECK(S >= 1, "pai_conv_dgrad_act_wthin: the slab buffer holds no slab (pai_conv_dgrad_act_wthin_slab_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    FwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x1 = dy; a.w = w_dgrad;
+    a.y1 = (void*)a1;           // never written: the tile has no store.  (Non-null: the body forms its addresses from it.)
+    a.bz = a1; a.bact1 = act1;
+    a.badd = add; a.bact2 = act2;
+    WThin wt;
+    wt.x1 = x1; wt.x2 = x2; wt.slab = slabs; wt.S = S; wt.TH = w.gt.H; wt.TW = w.gt.W;
+    hipError_t e = pai::memset_async(slabs, 0, (size_t)S * per, s);
+    PAI_CHECK(e == hipSuccess, "pai_conv_dgrad_act_wthin: hipMemsetAsync: %s", hipGetErrorString(e));
+    if (int rc = launch_fwd_mfma(w.g, a, w.p.mfma, s, &wt)) return rc;
+    // overwrite as pai_conv_wgrad_overwrite (1: dw and dbias are written) / _overwrite_w (2: dw written, dbias added to)
+    return launch_wthin_reduce(slabs, S, w.T, dw, dbias, overwrite != 0, overwrite == 1, s);
+}
+
 extern "C" int pai_conv_dgrad_bn_rows_max(const pai_conv_desc* d) {
     GG g;
     if (gg_build_dgrad(d, &g)) return -1;

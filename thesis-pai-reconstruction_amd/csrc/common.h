@@ -260,7 +260,19 @@ struct MfmaPlan {
 };
 enum WgradMfmaVariant { WG3_128x64 = 1, WG3_64x128, WG3_128x64_8, WGRAD_PATCH128, WGRAD_PATCH64, WGRAD_TILE128, WGRAD_TILE64 };
 MfmaPlan fwd_mfma_plan(const GG& g);
-int launch_fwd_mfma(const GG& g, const FwdArgs& a, const MfmaPlan& p, hipStream_t s);
+// The thin producer layer whose weight and bias gradient ride on the store of an input gradient (pai_conv_dgrad_act_wthin):
+// x1 | x2 are its one-channel inputs [N][TH][TW], `slab` holds S zeroed slabs of wthin_slab_floats(T) floats.
+struct WThin {
+    const void *x1, *x2;
+    float* slab;
+    int S, TH, TW;
+};
+static inline int wthin_slab_floats(int T) { return (16 * T + 1) * 64; }
+// turns the plan of an input gradient on 8 x 16-pixel, 64-channel patch tiles into its weight-gradient store form (T = 1 | 2
+// thin channels); false: the layer runs another variant, no such form exists
+bool fwd_mfma_wthin(MfmaPlan* p, int T);
+int launch_fwd_mfma(const GG& g, const FwdArgs& a, const MfmaPlan& p, hipStream_t s, const WThin* wt = nullptr);
+int launch_wthin_reduce(const float* slab, int S, int T, float* dw, float* dbias, int overwrite_w, int overwrite_bias, hipStream_t s);
 MfmaPlan wgrad_mfma_plan(const GG& g, bool has_dbias, bool has_prologue);
 bool wgrad_pro_ok(int dtype, const GG& g);
 // Per-device handle (pai_create / pai_bind): owner of the caller-provided split-K workspace and general scratch.

@@ -592,9 +592,15 @@ static int patch_rows(const GG& g, const FwdCfg& c, PatchGeo* pg) {
 // tap, ~30 vector instructions per 32 MFMAs) -- kept for the two configurations of eight / four 64 x 64 waves that sit AT
 // their occupancy's register line (128): unrolled, hipcc spills 12-15 registers there and reloads the fill constants from
 // scratch in front of every patch fill (same-box step: 6.68-6.74 ms against 6.55-6.59 with this form).
-template <int BM, int BN, bool DBB, int WN = 2, int WPX = 64, bool COLSWZ = true>   // DBB: two weight-tile buffers
-__device__ __forceinline__ void gg_fwd_patch_body(const GG& g, const FwdArgs& a, const PatchGeo& pg, int mtiles, int ntiles) {
+// WT > 0 (gg_dgrad_wthin_k): the tile is the output gradient of a thin (WT-channel) k4 s2 layer whose input needs no
+// gradient.  It is not stored: the layer's weight and bias gradient are formed from it, see the end of the body.
+constexpr int WTH_XROW = 160;                   // LDS bytes per row of the thin window: 80 pixels
+constexpr int WTH_XPLANE = 32 * WTH_XROW + 16;  // per thin channel: 32 rows (+ 16 B: the two planes on different banks)
+template <int BM, int BN, bool DBB, int WN = 2, int WPX = 64, bool COLSWZ = true, int WT = 0>   // DBB: two weight-tile buffers
+__device__ __forceinline__ void gg_fwd_patch_body(const GG& g, const FwdArgs& a, const PatchGeo& pg, int mtiles, int ntiles,
+                                                  const WThin& wt = WThin{}) {
     static_assert(WN == 2 || BN == 64, "one wave column: 64 output channels");
+    static_assert(WT == 0 || (BM == 128 && BN == 64 && WN == 2 && WPX == 64), "the weight-gradient store: 8 x 16 pixels, 64 channels");
     constexpr int abl = PATCH_ABL;
     typedef PatchDims<BM, WN, WPX> PD;
     constexpr int NTHR = PD::NTHR, MT = WPX / 16, NT = BN / (16 * WN);
@@ -1018,7 +1024,84 @@ __device__ __forceinline__ void gg_fwd_patch_body(const GG& g, const FwdArgs& a,
 #pragma unroll
     for (int k = 0; k < 8; ++k) bs1[k] = bs2[k] = 0.f;
     if (bwd) bwd_load_params(a, dcol + oc * 8, BP);
+    // WT: the window of the thin inputs under the tile -- output pixel (oy, ox) of the thin layer reads input rows 2 oy - 1 ..
+    // 2 oy + 2, and the tile holds every second output pixel: 32 rows x 64 columns per channel, fetched as 32 x 10 aligned
+    // 16-B chunks (columns 4 gx0 - 8 .. 4 gx0 + 71; a chunk lies inside the image or outside, outside is the zero padding)
+    unsigned char* Xs = smem + BM * CROW + (NTHR / 64) * 2 * BN * sizeof(float);   // behind the staged tile and the sums
+    if constexpr (WT > 0) {
+        const int iy0 = 4 * gy0 + 2 * g.poy[ph] - 1, ix0 = 4 * gx0 - 8;
+#pragma unroll
+        for (int i = 0; i < (320 * WT + NTHR - 1) / NTHR; ++i) {
+            const int q = tid + NTHR * i;
+            if (q < 320 * WT) {
+                const int t = q / 320, rem = q - t * 320, r = rem / 10, c = rem - r * 10;
+                const int iy = iy0 + r, ix = ix0 + 8 * c;
+                uint4 v = make_uint4(0u, 0u, 0u, 0u);
+                if ((unsigned)iy < (unsigned)wt.TH && (unsigned)ix < (unsigned)wt.TW)
+                    v = *(const uint4*)((const bf16_t*)(t ? wt.x2 : wt.x1) + ((size_t)(img * wt.TH + iy) * wt.TW + ix));
+                *(uint4*)(Xs + t * WTH_XPLANE + r * WTH_XROW + c * 16) = v;
+            }
+        }
+    }
     __syncthreads();
+    if constexpr (WT > 0) {
+        // The producer backward on the staged chunks, written back IN PLACE (a chunk has one owner): Cs then holds the tile
+        // as the two-launch path stores it, rounded to bf16.
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            static_assert(NP == NB, "every producer chunk was requested up front");
+            uint4* cp = (uint4*)(Cs + (orow0 + p * ORP) * CROW + oc * 16);
+            *cp = bap ? bwd_chunk_t<true, false>(*cp, zq[p], aq[p], sl1, sl2, BP, bs1, bs2)
+                      : bwd_chunk_t<false, false>(*cp, zq[p], aq[p], sl1, sl2, BP, bs1, bs2);
+        }
+        __syncthreads();
+        // dW[ch][k] += sum over the 128 pixels of tile[pixel][ch] * Xcol[pixel][k], k = tap * WT + t, as D = Xcol^T x tile on
+        // the matrix cores (thin_wgrad_k's arrangement): wave `wid` owns channels 16 wid .. + 15, a K step is 32 pixels (two
+        // tile rows); lane (fr, fq) gathers row k = 16 tt + fr of Xcol^T for its 8 pixels from the window and reads the
+        // tile transposed.  One more product with a row of ones gives the bias gradient.
+        const int tq = fr >> 2, tp = fr & 3;
+        const unsigned char* xb[WT];
+#pragma unroll
+        for (int tt = 0; tt < WT; ++tt) {
+            const int k = 16 * tt + fr, tap = k / WT, t = k - tap * WT, th = tap >> 2, tw = tap & 3;
+            xb[tt] = Xs + t * WTH_XPLANE + (4 * (fq >> 1) + th) * WTH_XROW + (7 + 2 * g.pox[ph] + tw + 32 * (fq & 1)) * 2;
+        }
+        const unsigned char* cb = Cs + (fq * 8 + tq) * CROW + (wid * 16 + 4 * tp) * 2;
+        const unsigned one2 = fr == 0 ? 0x3f803f80u : 0u;      // bf16 1.0 pairs in MFMA row 0
+        const bf8_t ones = __builtin_bit_cast(bf8_t, make_uint4(one2, one2, one2, one2));
+        f4_t wacc[WT], bacc = (f4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int tt = 0; tt < WT; ++tt) wacc[tt] = (f4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < BM / 32; ++ks) {
+            bf8_t bfr;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const bf4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+                    (bf4_t __attribute__((address_space(3)))*)(cb + (ks * 32 + h * 4) * CROW));
+#pragma unroll
+                for (int e = 0; e < 4; ++e) bfr[h * 4 + e] = v[e];
+            }
+#pragma unroll
+            for (int tt = 0; tt < WT; ++tt) {
+                typedef __attribute__((ext_vector_type(8))) unsigned short us8_t;
+                us8_t pv;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pv[j] = *(const unsigned short*)(xb[tt] + ks * 8 * WTH_XROW + j * 8);
+                wacc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8_t, pv), bfr, wacc[tt], 0, 0, 0);
+            }
+            bacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bfr, bacc, 0, 0, 0);
+        }
+        // wacc[tt][r] = D[k = 16 tt + 4 fq + r][channel 16 wid + fr].  Slab layout: register (wid, tt, r) of the 64 lanes is one
+        // contiguous 256-B row (the shape fp32 atomics run fastest at); wthin_reduce_k undoes the permutation.
+        float* slab = wt.slab + (size_t)(blockIdx.x % (unsigned)wt.S) * ((16 * WT + 1) * 64);
+#pragma unroll
+        for (int tt = 0; tt < WT; ++tt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) unsafeAtomicAdd(slab + ((wid * WT + tt) * 4 + r) * 64 + lane, wacc[tt][r]);
+        if (fq == 0) unsafeAtomicAdd(slab + 16 * WT * 64 + wid * 16 + fr, bacc[0]);
+        return;
+    }
     if (has_stats && tid < BN) {
         float* dst = a.stats + ((size_t)(ph * mtiles + bm) * 2) * g.Cout + n0 + tid;
         float s = 0.f, q = 0.f;
@@ -1075,6 +1158,51 @@ template <int BM, int BN, bool DBB>
 __global__ __launch_bounds__(BM, 3) void gg_fwd_patch1_k(GG g, FwdArgs a, PatchGeo pg, int mtiles, int ntiles) {
     gg_fwd_patch_body<BM, BN, DBB, 1>(g, a, pg, mtiles, ntiles);
 }
+// gg_fwd_patch_k<128, 64, false> with the weight-gradient store (body, WT): the input gradient of the layer behind a thin
+// first layer.  A kernel of its own, so that the plain input gradients keep their code and registers.
+template <int T>
+__global__ __launch_bounds__(256, 5) void gg_dgrad_wthin_k(GG g, FwdArgs a, PatchGeo pg, int mtiles, int ntiles, WThin wt) {
+    gg_fwd_patch_body<128, 64, false, 2, 64, true, T>(g, a, pg, mtiles, ntiles, wt);
+}
+// dw (+)= the S slabs summed in a fixed order; slab element (wave, tt, r, lane) is dW[16 wave + lane % 16][16 tt + 4 (lane / 16) + r]
+// (forward pack [64][16][T], k = tap * T + t), the last 64 elements are the bias gradient.  Thread = (element, one of four
+// ranges of slabs), eight loads in flight as in thin_wgrad_reduce_k.
+__global__ __launch_bounds__(256) void wthin_reduce_k(const float* slab, int S, int T, float* dw, float* dbias, int ow_w, int ow_b) {
+    __shared__ float red[4][64];
+    const int n = (16 * T + 1) * 64;
+    const int e = blockIdx.x * 64 + (threadIdx.x & 63), slice = threadIdx.x >> 6;
+    const int per = (S + 3) / 4, b0 = slice * per, b1 = min(S, b0 + per);
+    float sum = 0.f;
+    if (e < n) {
+        const float* src = slab + e;
+        int b = b0;
+        for (; b + 8 <= b1; b += 8) {
+            float t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) t[u] = src[(size_t)(b + u) * n];
+            sum += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
+        }
+        for (; b < b1; ++b) sum += src[(size_t)b * n];
+    }
+    red[slice][threadIdx.x & 63] = sum;
+    __syncthreads();
+    if (slice == 0 && e < n) {
+        sum = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+        if (e < 16 * T * 64) {
+            const int lane = e & 63, q = e >> 6, r = q & 3, tt = (q >> 2) % T, wave = (q >> 2) / T;
+            float* dst = dw + (16 * wave + (lane & 15)) * 16 * T + 16 * tt + 4 * (lane >> 4) + r;
+            *dst = ow_w ? sum : *dst + sum;
+        } else if (dbias) {
+            float* dst = dbias + (e - 16 * T * 64);
+            *dst = ow_b ? sum : *dst + sum;
+        }
+    }
+}
+int launch_wthin_reduce(const float* slab, int S, int T, float* dw, float* dbias, int overwrite_w, int overwrite_bias, hipStream_t s) {
+    PAI_LAUNCH(wthin_reduce_k, dim3(cdiv(wthin_slab_floats(T), 64)), dim3(256), 0, s, slab, S, T, dw, dbias, overwrite_w, overwrite_bias);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
 static size_t fwd_lds_bytes(int bm, int bn, bool db) {
     const size_t main_loop = (size_t)(db ? 2 : 1) * (bm * 128 + bn * 128);
     const size_t epilogue = bm * (bn * 2 + 16) + (bm / 64 * 2) * 2 * bn * sizeof(float);   // staged tile + [waves][2][BN]
@@ -1091,6 +1219,8 @@ static size_t fwd_lds_bytes(int bm, int bn, bool db) {
     X(FWD_PATCH256_DBB, PATCH, gg_fwd_patch_k, 256, 128, true)           \
     X(FWD_PATCH128_DBB, PATCH, gg_fwd_patch_k, 128, 128, true)           \
     X(FWD_PATCH128N, PATCH, gg_fwd_patch_k, 128, 64, false)              \
+    X(FWD_WTHIN1, WTHIN, gg_dgrad_wthin_k, 1)                            \
+    X(FWD_WTHIN2, WTHIN, gg_dgrad_wthin_k, 2)                            \
     X(FWD_TILE128, TILE, gg_fwd_mfma_k, 128, 128, false, false, 64)      \
     X(FWD_TILE64, TILE, gg_fwd_mfma_k, 128, 64, false, false, 64)
 #define X(id, form, k, ...) id,
@@ -1152,17 +1282,32 @@ MfmaPlan fwd_mfma_plan(const GG& g) {
     return p;
 }
 
+bool fwd_mfma_wthin(MfmaPlan* p, int T) {
+    if (p->variant != FWD_PATCH128N || p->ntiles != 1 || (T != 1 && T != 2)) return false;
+    p->variant = T == 1 ? FWD_WTHIN1 : FWD_WTHIN2;
+    p->name = fwd_mfma_names[p->variant];
+    // the epilogue keeps the window of the thin inputs behind the staged tile and its sums (gg_fwd_patch_body, Xs)
+    const size_t epi = 128 * (64 * 2 + 16) + 4 * 2 * 64 * sizeof(float) + (size_t)T * WTH_XPLANE;
+    if (epi > p->lds) p->lds = epi;
+    return true;
+}
+
 static int fwd_lds_opt_in();     // (defined below the switch, so that the kernels keep their order in the code object)
-int launch_fwd_mfma(const GG& g, const FwdArgs& a, const MfmaPlan& p, hipStream_t s) {
+int launch_fwd_mfma(const GG& g, const FwdArgs& a, const MfmaPlan& p, hipStream_t s, const WThin* wt) {
     float* ws = pai_ctx()->workspace;
+    const bool wthin = p.variant == FWD_WTHIN1 || p.variant == FWD_WTHIN2;
+    PAI_CHECK(wthin == (wt != nullptr), "launch_fwd_mfma: the weight-gradient store and its arguments go together");
+    const WThin wta = wt ? *wt : WThin{};
     if (p.lds > 64 * 1024 && fwd_lds_opt_in()) return 1;
 #define FWD_LAUNCH_TILE(k, ...) PAI_LAUNCH((k<__VA_ARGS__>), p.grid, p.block, p.lds, s, g, a, p.mtiles, p.ntiles, p.ksplit, ws)
 #define FWD_LAUNCH_PATCH(k, ...) PAI_LAUNCH((k<__VA_ARGS__>), p.grid, p.block, p.lds, s, g, a, p.pg, p.mtiles, p.ntiles)
+#define FWD_LAUNCH_WTHIN(k, ...) PAI_LAUNCH((k<__VA_ARGS__>), p.grid, p.block, p.lds, s, g, a, p.pg, p.mtiles, p.ntiles, wta)
 #define X(id, form, k, ...) case id: FWD_LAUNCH_##form(k, __VA_ARGS__); break;
     switch (p.variant) { FWD_MFMA_VARIANTS(X) }
 #undef X
 #undef FWD_LAUNCH_TILE
 #undef FWD_LAUNCH_PATCH
+#undef FWD_LAUNCH_WTHIN
     PAI_LAUNCH_CHECK();
     if (p.ksplit > 1)
         PAI_LAUNCH(splitk_finish_k, dim3(p.rows, g.nphase, cdiv(g.Cout, FIN_COLS)), dim3(256), 0, s, g, a, ws, p.rows, p.ksplit);

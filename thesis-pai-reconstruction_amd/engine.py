@@ -569,7 +569,9 @@ class UnetEngine:
         # dz is read by the side-stream weight gradient while the main stream moves on: one per layer
         G["dz_head"] = torch.empty(S["pred"].numel(), dtype=dt, device=dev)
         G["dz_dec"] = [torch.empty_like(S["w"][j]) if j < L - 1 else None for j in range(L)]
-        G["dz_enc"] = [torch.empty_like(S["z"][i]) for i in range(L)]
+        # (dz of encoder 0, the widest one, is allocated by the pass that stores it: ``backward`` with the fused first-layer
+        #  weight gradient does not)
+        G["dz_enc"] = [torch.empty_like(S["z"][i]) if i > 0 else None for i in range(L)]
         S["grads"] = G
         return G
 
@@ -809,11 +811,22 @@ class UnetEngine:
         wgrad(d, S["a"][i - 1], None, dz, conv, True)
         _, wd = self.enc_packs[i].get(dtype)
 
+        enc0_fused = ops.conv_dgrad_act_wthin_ok(P["enc_desc"][1], P["enc_desc"][0], False)
+
         def enc_dgrad(i, dz, wd):
             """Input gradient of encoder i; producer = encoder i-1, read through LeakyReLU here and through
             ReLU (raw for encoder 0) by its skip decoder: du = lrelu'(pre) * g + relu'(pre) * g_skip."""
             d = P["enc_desc"][i]
+            if i - 1 == 0 and enc0_fused:
+                # encoder 0's input is the image: its dz has one reader, its own weight gradient -- formed in this store
+                # (pai_conv_dgrad_act_wthin), dz_enc[0] is not written
+                c0, d0 = self.enc_conv[0], P["enc_desc"][0]
+                ops.conv_dgrad_act_wthin(d, dz, wd, S["z"][0], ACT_LRELU, G["gskip"][0], ACT_NONE, d0, S["x"], None,
+                                         A.seg(c0.weight), A.seg(c0.bias), wthin_slabs(P, d, d0))
+                return 0
             if i - 1 == 0:   # bare Conv2d: no norm; the gradient written IS dz of encoder 0
+                if G["dz_enc"][0] is None:
+                    G["dz_enc"][0] = torch.empty_like(S["z"][0])
                 return ops.conv_dgrad_bn(d, dz, wd, G["dz_enc"][0], None, S["z"][0], ACT_LRELU, G["gskip"][0], ACT_NONE)
             pst, pbn = S["ebn"][i - 1], self.enc_bn[i - 1]
             ops.conv_dgrad_bn_apply(d, dz, wd, G["ga"][i - 1], None, S["z"][i - 1], ACT_LRELU, G["gskip"][i - 1], ACT_RELU,
@@ -837,11 +850,21 @@ class UnetEngine:
         # encoder 0 (its dz came out of encoder 1's input gradient): on the tail stream, beside encoder 1's
         conv0 = self.enc_conv[0]
         flush_held()
-        with torch.cuda.stream(side.fork_tail()):
-            (ops.conv_wgrad if min(_cin_cout(conv0)) <= 2 else conv_wgrad)(
-                P["enc_desc"][0], S["x"], None, G["dz_enc"][0], A.seg(conv0.weight), A.seg(conv0.bias))
+        if not enc0_fused:
+            with torch.cuda.stream(side.fork_tail()):
+                (ops.conv_wgrad if min(_cin_cout(conv0)) <= 2 else conv_wgrad)(
+                    P["enc_desc"][0], S["x"], None, G["dz_enc"][0], A.seg(conv0.weight), A.seg(conv0.bias))
         side.join()
         done(conv0.bias)      # both side streams have been joined: the whole arena is final
+
+
+def wthin_slabs(P, d, d_thin):
+    """fp32 slab scratch of ``ops.conv_dgrad_act_wthin`` for the plan ``P`` of an engine (one buffer per plan: a recorded
+    launch plan keeps its address)."""
+    if "wthin_slabs" not in P:
+        P["wthin_slabs"] = torch.empty(ops.conv_dgrad_act_wthin_slab_bytes(d, d_thin) // 4, dtype=torch.float32,
+                                       device=P["device"])
+    return P["wthin_slabs"]
 
 
 # --------------------------------------------------------------------------------------
@@ -983,11 +1006,19 @@ class DiscEngine:
     def _grads(self, S):
         if S["grads"] is None:
             P = S["P"]
-            S["grads"] = {"du": [torch.empty_like(a) for a in S["a"]],
+            # du[0], the widest one, is allocated when a pass first stores it (``_du0``): the D-phase pass does not
+            S["grads"] = {"du": [None] + [torch.empty_like(a) for a in S["a"][1:]],
                           "dl": torch.empty(S["logits"].numel(), dtype=P["dtype"], device=P["device"]),
                           "dl32": torch.empty(S["logits"].numel(), dtype=torch.float32, device=P["device"]),
                           "dy": torch.empty(P["N"] * P["H"] * P["W"] * self.in_ch, dtype=P["dtype"], device=P["device"])}
         return S["grads"]
+
+    @staticmethod
+    def _du0(S):
+        G = S["grads"]
+        if G["du"][0] is None:
+            G["du"][0] = torch.empty_like(S["a"][0])
+        return G["du"][0]
 
     def forward_loss(self, x, y, dtype, y2, n_first, target_first, target_rest, acc, need_grad: bool):
         """The forward pass with the BCE-with-logits loss of its logits against a per-image constant target (images below
@@ -1061,30 +1092,40 @@ class DiscEngine:
         # du[k] = LeakyReLU'(a[k]) * dgrad of block k+1: the activation backward rides on the dgrad store
         if not head_done:
             ops.conv_dgrad_act(d, dl, wd, G["du"][3], None, S["a"][3], ACT_LRELU)
+        # Block 0's input needs no gradient in the D phase: its weight gradient is then formed in the store of block 1's input
+        # gradient (pai_conv_dgrad_act_wthin) -- du[0] is neither written nor read back, and no tail-stream launch ends the pass.
+        wthin = need_params and not need_dy and ops.conv_dgrad_act_wthin_ok(P["desc"][1], P["desc"][0], need_dy)
         for k in range(3, -1, -1):
             conv = self.convs[k]
             d = P["desc"][k]
+            if wthin and k == 0:
+                break
             if need_params and k == 0:
                 # thin first layer: tail stream, beside block 1's weight gradient; its hook fires after the join
                 with torch.cuda.stream(side.fork_tail()):
                     (ops.conv_wgrad if min(_cin_cout(conv)) <= 2 else conv_wgrad)(
-                        d, S["xin"], S["yin"], G["du"][0], A.seg(conv.weight), A.seg(conv.bias))
+                        d, S["xin"], S["yin"], self._du0(S), A.seg(conv.weight), A.seg(conv.bias))
             elif need_params:
                 with torch.cuda.stream(side.fork(d)):
                     conv_wgrad(self._wgrad_desc(P, k), S["a"][k - 1], None, G["du"][k], A.seg(conv.weight), A.seg(conv.bias))
                     if hook is not None:
                         hook(A, A.end_of(conv.bias))
-            if k > 0:
+            if k == 1 and wthin:
+                _, wd = self.packs[1].get(dtype)
+                c0, d0 = self.convs[0], P["desc"][0]
+                ops.conv_dgrad_act_wthin(d, G["du"][1], wd, S["a"][0], ACT_LRELU, None, ACT_NONE, d0, S["xin"], S["yin"],
+                                         A.seg(c0.weight), A.seg(c0.bias), wthin_slabs(P, d, d0))    # thin: added
+            elif k > 0:
                 _, wd = self.packs[k].get(dtype)
-                ops.conv_dgrad_act(d, G["du"][k], wd, G["du"][k - 1], None, S["a"][k - 1], ACT_LRELU)
+                ops.conv_dgrad_act(d, G["du"][k], wd, self._du0(S) if k == 1 else G["du"][k - 1], None, S["a"][k - 1], ACT_LRELU)
             elif need_dy:
                 _, wd = self.packs[0].get(dtype)
                 if addend is not None and self.in_ch == 1 and self.fused_enabled() and addend.dtype == torch.float32 \
                         and addend.is_contiguous() and addend.numel() == N * H * W and ops.conv_dgrad_f32add_ok(d):
                     gy = torch.empty(N * H * W, dtype=torch.float32, device=dev)
-                    ops.conv_dgrad_f32add(d, G["du"][0], wd, addend, gy)      # fp32 + addend in the store
+                    ops.conv_dgrad_f32add(d, self._du0(S), wd, addend, gy)      # fp32 + addend in the store
                 else:
-                    ops.conv_dgrad(d, G["du"][0], wd, None, G["dy"], only_c2=True)
+                    ops.conv_dgrad(d, self._du0(S), wd, None, G["dy"], only_c2=True)
         side.join()
         if need_params and hook is not None:
             hook(A, A.end_of(self.convs[0].bias))

@@ -83,6 +83,10 @@ SIGNATURES = {
     "pai_conv_fwd": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pai_conv_dgrad": (_I, [_D, _P, _P, _P, _P, _I, _P]),
     "pai_conv_dgrad_act": (_I, [_D, _P, _P, _P, _P, _P, _I, _P]),
+    "pai_conv_dgrad_act_wthin_ok": (_I, [_D, _D, _I]),
+    "pai_conv_dgrad_act_wthin_slab_bytes": (_L, [_D, _D]),
+    "pai_conv_dgrad_act_wthin_kernel_name": (_I, [_D, _D, C.c_char_p, _I]),
+    "pai_conv_dgrad_act_wthin": (_I, [_D, _P, _P, _P, _I, _P, _I, _D, _P, _P, _P, _P, _I, _P, _L, _P]),
     "pai_conv_dgrad_f32add_ok": (_I, [_D]),
     "pai_conv_dgrad_f32add": (_I, [_D, _P, _P, _P, _P, _P]),
     "pai_head_loss_ok": (_I, [_D, _I]),

@@ -351,6 +351,62 @@ def conv_dgrad_act(d, dy, w_dgrad, dx1, dx2, a1, act1):
                                             _stream()), "pai_conv_dgrad_act")
 
 
+def conv_dgrad_act_wthin_ok(d, d_thin, need_dx: bool = False) -> bool:
+    """``conv_dgrad_act_wthin`` takes this pair of layers and the caller does not need the gradient tensor between them
+    (pai_conv_dgrad_act_wthin_ok; host only; reads the tunable ``dgrad_wthin``)."""
+    return bool(L.load().pai_conv_dgrad_act_wthin_ok(C.byref(d), C.byref(d_thin), int(bool(need_dx))))
+
+
+def conv_dgrad_act_wthin_slab_bytes(d, d_thin) -> int:
+    """Bytes of fp32 slab scratch ``conv_dgrad_act_wthin`` wants for this pair (pai_conv_dgrad_act_wthin_slab_bytes)."""
+    n = L.load().pai_conv_dgrad_act_wthin_slab_bytes(C.byref(d), C.byref(d_thin))
+    if n < 0:
+        raise PaiError("pai_conv_dgrad_act_wthin_slab_bytes: not a pair of layers conv_dgrad_act_wthin takes")
+    return n
+
+
+def conv_dgrad_act_wthin_kernel_name(d, d_thin) -> str:
+    buf = C.create_string_buffer(96)
+    if L.load().pai_conv_dgrad_act_wthin_kernel_name(C.byref(d), C.byref(d_thin), buf, 96) != 0:
+        raise PaiError("pai_conv_dgrad_act_wthin_kernel_name: not a pair of layers conv_dgrad_act_wthin takes")
+    return buf.value.decode()
+
+
+class _TimedWthin(_Timed):
+    """``_Timed`` for the launch that has a name of its own: the input gradient's FLOPs under the symbol it runs as."""
+
+    def __init__(self, d, d_thin):
+        super().__init__(d, 1)
+        self.d_thin = d_thin
+
+    def __exit__(self, *exc):
+        if self.on:
+            LaunchTimer.disarm()
+            PROFILE.append((conv_dgrad_act_wthin_kernel_name(self.d, self.d_thin), 1, conv_flops(self.d), self.t, self.t))
+        return False
+
+
+def conv_dgrad_act_wthin(d, dy, w_dgrad, a1, act1, add, act2, d_thin, x1, x2, dw, dbias, slabs, overwrite=0):
+    """The input gradient of layer ``d`` with act1'(a1) (+ act2'(a1) * add) applied, NOT stored: the weight and bias gradient
+    of the thin layer ``d_thin`` in front of it (inputs x1 | x2) are formed from its tiles and added to (``overwrite`` 0) or
+    written into (1; 2: dw written, dbias added to) dw / dbias.  conv_dgrad_act + conv_wgrad without the tensor between them
+    (pai_conv_dgrad_act_wthin).  ``slabs``: fp32 scratch of ``conv_dgrad_act_wthin_slab_bytes``."""
+    if not isinstance(d_thin, ConvDesc) or not isinstance(d, ConvDesc):
+        raise PaiError("conv_dgrad_act_wthin: d and d_thin are convolution descriptors (make_desc)")
+    if slabs is None or slabs.dtype != torch.float32 or not slabs.is_contiguous():
+        raise PaiError("conv_dgrad_act_wthin: slabs is a contiguous fp32 tensor")
+    if (x2 is None) != (d_thin.C2 == 0):
+        raise PaiError("conv_dgrad_act_wthin: x2 goes with the thin layer's second channel")
+    if dw.numel() != d_thin.Cout * 16 * (d_thin.C1 + d_thin.C2) or (dbias is not None and dbias.numel() != d_thin.Cout):
+        raise PaiError("conv_dgrad_act_wthin: dw / dbias do not have the thin layer's shape")
+    with _TimedWthin(d, d_thin):
+        L.check(L.load().pai_conv_dgrad_act_wthin(C.byref(d), _p(dy), _p(w_dgrad), _p(a1), int(act1), _p(add), int(act2),
+                                                  C.byref(d_thin), _p(x1, torch.bfloat16), _p(x2, torch.bfloat16),
+                                                  _p(dw, torch.float32), _p(dbias, torch.float32), int(overwrite),
+                                                  _p(slabs, torch.float32), slabs.numel() * 4, _stream()),
+                "pai_conv_dgrad_act_wthin")
+
+
 def conv_dgrad_f32add_ok(d) -> bool:
     """The only_c2 input gradient of this layer can be stored as fp32 with an addend (pai_conv_dgrad_f32add_ok; host only)."""
     return bool(L.load().pai_conv_dgrad_f32add_ok(C.byref(d)))
