@@ -951,6 +951,56 @@ int pai_palette_objective(const float* model_out, const float* noise, const floa
                           const float* table, int T, int N, int64_t P, int C, int learn_var, float vlb_weight, float* out,
                           float* dout, float* ws, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Device random numbers (added under ABI 141, no version change; csrc/philox.h): Philox4x32-10 inside the kernels, so that a
+ * random value is a pure function of (seed, step, site, element index).  Nothing random is stored; the backward of a dropout
+ * site regenerates the keep bits of its forward; a run is reproducible from the two integers seed and step.
+ * Addressing, the same in every entry point: key = (seed low 32 bits, seed high 32 bits), counter = (block, sub, stream,
+ * step).  block = flat element index / 4 (/ 8 for keep bits) of the tensor as it lies in memory (NHWC activations, [N][P][C]
+ * pixels); sub = 0 except in the sampler, where it is the draw index k (0: y_T, k: the k-th reverse step); stream: 0 = t, 1 = u,
+ * 2 = z of the noising, 3 = sampler noise, 16 + i = the dropout of the i-th ResBlock; step = the training step or the index of
+ * the sampling call, held on the host and passed by value (no device-to-host copy, no synchronisation).  A tensor that needs
+ * more than 2^32 blocks is refused.  Derived values, w a word of the block:
+ *     raw       w itself, four per block
+ *     uniform   (w >> 8) 2^-24 in [0, 1), exact; four per block
+ *     integer   umulhi(w, T) in [0, T); four per block
+ *     keep      eight per block: lane j = (w[j / 2] >> 16 (j % 2)) & 0xffff, kept iff lane >= thr, thr = round(p 65536)
+ *     normal    four per block, Box-Muller on (w0, w1) -> (z0, z1) and (w2, w3) -> (z2, z3): u1 = ((w0 >> 9) + 1) 2^-23 in
+ *               (0, 1], v = (w1 >> 8) 2^-24, r = sqrtf(-2 logf(u1)), sincospif(2 v): z0 = r cos, z1 = r sin (full precision)
+ * pai_philox_fill: out[0 .. n) of the kind's type (raw uint32, uniform fp32, normal fp32, integer int32 with param = T >= 1,
+ * keep uint8 0 / 1 with param = thr <= 65536) for the tuple (seed, sub, stream, step); any n >= 1, the tail of the last block
+ * element by element; out aligned to its element type.  This is the surface the generator is pinned through, and a utility.
+ * pai_film_norm_fwd_rng / pai_film_norm_bwd_rng: pai_film_norm_fwd / _bwd with (seed, stream, step, thr) in place of mask
+ * (sub = 0): the forward and the reduce and apply launches of the backward each rebuild the eight keep flags of a vector
+ * from one block while its loads are in flight; no mask tensor exists.  The kernel bodies are those of the mask forms (a
+ * template parameter says where the flags come from), so the result has the bits of the mask form on the same flags.
+ * keep_scale is always applied.  N rows C / 8 <= 2^32.
+ * pai_palette_noise_rng: pai_palette_noise with t, u and z drawn inside the launch: t[n] = integer n of stream 0 (T), u[n] =
+ * uniform n of stream 1, z = the normals of stream 2 over the flat [N][P][C] tensor, all with sub = 0.  Every workgroup of
+ * sample n recomputes that sample's t and u; one of them writes t[n] (int32, for pai_palette_objective) and gamma[n].  The
+ * arithmetic after the draws is that of pai_palette_noise.
+ * pai_palette_step_rng: pai_palette_step with noise = the normals of (seed, sub, stream 3, step) over the flat [pixel][C]
+ * tensor in place of the noise tensor (not formed when add_noise is 0). */
+#define PAI_PHILOX_RAW 0
+#define PAI_PHILOX_UNIFORM 1
+#define PAI_PHILOX_NORMAL 2
+#define PAI_PHILOX_INT 3
+#define PAI_PHILOX_KEEP 4
+int pai_philox_fill(int kind, void* out, int64_t n, uint64_t seed, uint32_t sub, uint32_t stream, uint32_t step,
+                    uint32_t param, void* stream_handle);
+int pai_film_norm_fwd_rng(int dtype, const void* x, int64_t rows, int N, int C, const float* mean, const float* rstd,
+                          const float* gamma, const float* beta, const void* emb, int64_t ld, uint64_t seed, uint32_t stream,
+                          uint32_t step, uint32_t thr, float keep_scale, int act, void* out, void* stream_handle);
+int pai_film_norm_bwd_rng(int dtype, const void* g, const void* x, int64_t rows, int N, int C, const float* mean,
+                          const float* rstd, const float* gamma, const float* beta, const void* emb, int64_t ld, uint64_t seed,
+                          uint32_t stream, uint32_t step, uint32_t thr, float keep_scale, int act, void* dx, void* demb,
+                          float* dgamma, float* dbeta, float* ws, void* stream_handle);
+int pai_palette_noise_rng(const float* y0, const float* gammas, const float* gammas_prev, int T, int N, int64_t P, int C,
+                          uint64_t seed, uint32_t step, int32_t* t, float* y_t, float* noise, float* gamma, void* stream_handle);
+int pai_palette_step_rng(int dtype, const void* model_out, const float* y_t, int64_t pixels, int C, int learn_var,
+                         int add_noise, float s1, float rs, float c0, float c1, float log_lo, float log_hi, uint64_t seed,
+                         uint32_t sub, uint32_t step, float* y_next, void* xy_next, void* stream_handle);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,8 +14,12 @@ Random normal data throughout (never zeros: MI355X_MICROARCH, data-dependent pow
     python scripts/bench_palette.py [--precision bf16-mixed] [--batch 8] [--size 256] [--steps 100] [--mults 1,1,2,2,4,4]
                                     [--attention-res 16,8] [--no-sampler] [--no-attention] [--forward-only K]
                                     [--no-film-norm] [--film-norm-only] [--train] [--train-only] [--train-batch 4]
-                                    [--count-launches]
+                                    [--count-launches] [--device-rng]
 
+``--device-rng`` adds a line after every film_norm row (``film_norm_device_rng``: the mask forms, the ``_rng`` forms and the three
+torch launches that draw a mask, timed in turn on the same tensors; ``parent_path_ms`` = draw + forward + backward with a mask
+against ``rng_path_ms`` = the two ``_rng`` calls) and a second sampling call with ``Palette.device_rng`` set
+(``palette_sample_device_rng``).
 ``--forward-only K`` runs K U-Net forward passes and nothing else (the run to put under a kernel trace); ``--film-norm-only``
 runs the film_norm rows and nothing else (no model is built).
 """
@@ -96,7 +100,33 @@ def bench_attention_bwd(dtype, n, heads, T, ch, qkv, iters):
 FILM_NORM_SHAPES = [(65536, 64), (16384, 128), (1024, 256), (256, 256)]      # (rows, C) per sample: the class defaults at 256 x 256
 
 
-def bench_film_norm(dtype, n):
+def bench_film_norm_rng(dtype, n, rows, C, t):
+    """The --device-rng line of one shape: the mask forms, the _rng forms (keep bits from csrc/philox.h, no mask tensor) and
+    the three torch launches that draw a mask, timed in turn on the same tensors, three rounds, the median of each."""
+    x, g, emb, gamma, beta, mask, keep, mean, rstd, out, dx, demb, dgb, ws, iters = t
+    thr, seed = ops.dropout_thr(0.1), 0x9E3779B97F4A7C15
+    runs = {
+        "mask_fwd_ms": lambda: ops.film_norm_fwd(dtype, x, rows, n, C, mean, rstd, gamma, beta, emb, 2 * C, mask, keep, ops.ACT_SILU, out),
+        "rng_fwd_ms": lambda: ops.film_norm_fwd_rng(dtype, x, rows, n, C, mean, rstd, gamma, beta, emb, 2 * C, seed, 16, 1, thr, keep,
+                                                    ops.ACT_SILU, out),
+        "mask_bwd_ms": lambda: ops.film_norm_bwd(dtype, g, x, rows, n, C, mean, rstd, gamma, beta, emb, 2 * C, mask, keep, ops.ACT_SILU,
+                                                 dx, demb, dgb[:C], dgb[C:], ws),
+        "rng_bwd_ms": lambda: ops.film_norm_bwd_rng(dtype, g, x, rows, n, C, mean, rstd, gamma, beta, emb, 2 * C, seed, 16, 1, thr, keep,
+                                                    ops.ACT_SILU, dx, demb, dgb[:C], dgb[C:], ws),
+        "mask_draw_ms": lambda: (torch.rand(x.shape, device=x.device) >= 0.1).to(torch.uint8),
+    }
+    seen = {k: [] for k in runs}
+    for _ in range(3):
+        for k, fn in runs.items():
+            seen[k].append(timed(fn, 3, iters))
+    row = {"bench": "film_norm_device_rng", "dtype": str(dtype), "N": n, "rows": rows, "C": C}
+    row.update({k: round(sorted(v)[1], 4) for k, v in seen.items()})
+    row["parent_path_ms"] = round(row["mask_draw_ms"] + row["mask_fwd_ms"] + row["mask_bwd_ms"], 4)
+    row["rng_path_ms"] = round(row["rng_fwd_ms"] + row["rng_bwd_ms"], 4)
+    print(json.dumps(row), flush=True)
+
+
+def bench_film_norm(dtype, n, device_rng=False):
     es = torch.empty(0, dtype=dtype).element_size()
     for rows, C in FILM_NORM_SHAPES:
         numel = n * rows * C
@@ -135,6 +165,8 @@ def bench_film_norm(dtype, n):
         row.update(torch_fwd_ms=round(tf, 4), torch_fwd_GBps=round(fwd_bytes / tf / 1e6, 1), torch_bwd_ms=round(tb, 4),
                    torch_bwd_GBps=round(bwd_bytes / tb / 1e6, 1))
         print(json.dumps(row), flush=True)
+        if device_rng:
+            bench_film_norm_rng(dtype, n, rows, C, (x, g, emb, gamma, beta, mask, keep, mean, rstd, out, dx, demb, dgb, ws, iters))
 
 
 AVGPOOL_SHAPES = [(256, 128), (128, 128), (64, 256), (32, 256), (16, 512)]     # (H = W of dx, C): the class defaults at 256 x 256
@@ -202,6 +234,8 @@ def main():
     ap.add_argument("--forward-only", type=int, default=0)
     ap.add_argument("--no-film-norm", action="store_true")
     ap.add_argument("--film-norm-only", action="store_true")
+    ap.add_argument("--device-rng", action="store_true",
+                    help="add a line with the device generator (pai.DeviceRNG) to the film-norm and sampler timings")
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--train-only", action="store_true")
     ap.add_argument("--train-batch", type=int, default=4)
@@ -214,7 +248,7 @@ def main():
         return
     if a.film_norm_only:
         torch.manual_seed(0)
-        bench_film_norm(torch.bfloat16, a.batch)
+        bench_film_norm(torch.bfloat16, a.batch, a.device_rng)
         return
     torch.manual_seed(0)
     dev = torch.device("cuda:0")
@@ -245,10 +279,17 @@ def main():
         print(json.dumps({"bench": "palette_sample", "precision": a.precision, "N": a.batch, "size": a.size, "steps": a.steps,
                           "seconds": round(ms / 1e3, 3), "images_per_s": round(a.batch / (ms / 1e3), 3),
                           "ms_per_unet_forward": round(ms / a.steps, 3)}), flush=True)
+        if a.device_rng:
+            model.device_rng = pai.DeviceRNG(0)
+            ms = timed(lambda: model(x), 1, 1)
+            model.device_rng = None
+            print(json.dumps({"bench": "palette_sample_device_rng", "precision": a.precision, "N": a.batch, "size": a.size,
+                              "steps": a.steps, "seconds": round(ms / 1e3, 3), "images_per_s": round(a.batch / (ms / 1e3), 3),
+                              "ms_per_unet_forward": round(ms / a.steps, 3)}), flush=True)
     if not a.no_attention:
         bench_attention(dtype, a.batch, 4)
     if not a.no_film_norm:
-        bench_film_norm(torch.bfloat16, a.batch)
+        bench_film_norm(torch.bfloat16, a.batch, a.device_rng)
     if a.train:
         del model
         bench_train(a, mults, att)

@@ -8,6 +8,16 @@ The loop is the one main.py does not have for this model: draw t, noise the targ
 variational-bound objective, backward, Adam, LinearLR -- all inside ``fit_step``, which returns the loss as a device scalar.
 The loss is copied to the host only every ``--log-every`` steps.  The checkpoint goes to logs/NAME/palette.ckpt (or ``--out``)
 with the hyper-parameters, the weights, the optimizer and scheduler states and the step count.
+
+    python scripts/train_palette.py NAME --synthetic 64 --steps 200 --device-rng --seed 7
+    python scripts/train_palette.py NAME --synthetic 64 --steps 400 --device-rng --resume logs/NAME/palette.ckpt
+
+``--device-rng`` (default off) draws t, u, z and every dropout mask inside the kernels from ``pai.DeviceRNG(--seed)`` instead of
+torch's generator; the checkpoint then also holds the generator's two integers (``device_rng``).  ``--resume CKPT`` restores
+model, optimizer, scheduler, step count and that state and trains on to ``--steps``; with the device generator the draws of
+step k are the same whether or not the run was interrupted before it.  The batches are not: the checkpoint holds the epoch
+count, not the position inside an epoch, so a run resumed away from an epoch boundary starts a new epoch.  A checkpoint that
+holds rng state is resumed with ``--device-rng`` only.
 """
 import argparse
 import os
@@ -46,6 +56,9 @@ def build_parser():
     p.add_argument("--inference-steps", default=100, type=int)
     p.add_argument("--log-every", default=10, type=int)
     p.add_argument("--seed", default=0, type=int)
+    p.add_argument("--device-rng", default=False, action=argparse.BooleanOptionalAction,
+                   help="draw inside the kernels from pai.DeviceRNG(--seed); its state goes into the checkpoint")
+    p.add_argument("--resume", type=pathlib.Path, help="checkpoint of this script to continue from")
     p.add_argument("--out", type=pathlib.Path, help="checkpoint path (default logs/NAME/palette.ckpt)")
     return p
 
@@ -72,6 +85,24 @@ def main(args):
     loader = data.train_dataloader()
     (opt,), (sched,) = model.make_optimizers()
     step, epoch, loss = 0, 0, None
+    if args.device_rng:
+        model.device_rng = pai.DeviceRNG(args.seed)
+    if args.resume is not None:
+        ckpt = torch.load(str(args.resume), map_location="cpu", weights_only=False)
+        model.load_state_dict(ckpt["state_dict"])
+        opt.load_state_dict(ckpt["optimizer_states"][0])
+        sched.load_state_dict(ckpt["lr_schedulers"][0])
+        step, epoch = int(ckpt["global_step"]), int(ckpt["epoch"])
+        if args.device_rng:
+            if "device_rng" not in ckpt:
+                raise SystemExit(f"{args.resume} holds no device_rng state: it was not trained with --device-rng")
+            model.device_rng.load_state_dict(ckpt["device_rng"])
+        elif "device_rng" in ckpt:
+            raise SystemExit(f"{args.resume} was trained with --device-rng: resume it with --device-rng (its draws continue from "
+                             f"the stored state), not with torch's generator")
+        print(f"resumed {args.resume} at step {step}", flush=True)
+        if step >= args.steps:
+            raise SystemExit(f"{args.resume} is already at step {step}: nothing to do for --steps {args.steps}")
     while step < args.steps:
         if hasattr(loader, "set_epoch"):
             loader.set_epoch(epoch)
@@ -93,7 +124,8 @@ def main(args):
     tmp = str(out) + ".tmp"
     torch.save({"epoch": epoch, "global_step": step, "hyper_parameters": model.hparams,
                 "state_dict": {k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()},
-                "optimizer_states": [opt.state_dict()], "lr_schedulers": [sched.state_dict()]}, tmp)
+                "optimizer_states": [opt.state_dict()], "lr_schedulers": [sched.state_dict()],
+                **({"device_rng": model.device_rng.state_dict()} if model.device_rng is not None else {})}, tmp)
     os.replace(tmp, str(out))
     print(f"wrote {out} after {step} steps, loss {float(loss):.5g}", flush=True)
     return {"checkpoint": str(out), "steps": step, "loss": float(loss)}

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpai_hip.so")
 STAMPS = os.path.join(CSRC, ".build_stamps.json")     # object / library -> content hash of what it was built from
-SOURCES = ["api.hip", "gg_simt.hip", "gg_mfma.hip", "gg_wg3.hip", "gg_thin.hip", "head.hip", "gg_small.hip", "gg_group.hip", "gg_pw.hip", "bn.hip", "ew_stream.hip", "gate.hip", "resnet.hip", "inorm.hip", "vit.hip", "loss.hip", "ssim.hip", "eval.hip", "misc.hip", "comm.hip", "plan.hip", "data.hip", "palette.hip", "film_norm.hip"]
+SOURCES = ["api.hip", "gg_simt.hip", "gg_mfma.hip", "gg_wg3.hip", "gg_thin.hip", "head.hip", "gg_small.hip", "gg_group.hip", "gg_pw.hip", "bn.hip", "ew_stream.hip", "gate.hip", "resnet.hip", "inorm.hip", "vit.hip", "loss.hip", "ssim.hip", "eval.hip", "misc.hip", "comm.hip", "plan.hip", "data.hip", "palette.hip", "film_norm.hip", "philox.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "plan.h"), os.path.join(CSRC, "gg_tile.h"), os.path.join(HERE, "..", "include", "pai_hip.h")]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in the (unified) VGPR file.  Without it hipcc 7.2
 # put the wgrad accumulators in AGPRs with a different source/destination register per MFMA and
@@ -26,6 +26,8 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # 118-157 registers around the fused producer-backward store (0-4 without the pass), and packed fp32 instructions are the
 # slow form beside MFMAs anyway (CDNA4 guide, cycle constants).
 EXTRA_FLAGS = {"gg_mfma.hip": ["-fno-slp-vectorize"]}
+# Headers only some sources include: a change rebuilds those alone.
+EXTRA_HEADERS = {"palette.hip": ["philox.h"], "film_norm.hip": ["philox.h"], "philox.hip": ["philox.h"]}
 
 
 def _hipcc():
@@ -72,7 +74,8 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
         o = os.path.join(CSRC, src.replace(".hip", ".o"))
         objs.append(o)
         flags = FLAGS + EXTRA_FLAGS.get(src, [])
-        new[os.path.basename(o)] = _digest([s] + HEADERS, " ".join(flags))
+        new[os.path.basename(o)] = _digest([s] + HEADERS + [os.path.join(CSRC, h) for h in EXTRA_HEADERS.get(src, [])],
+                                                " ".join(flags))
         if force or not os.path.exists(o) or stamps.get(os.path.basename(o)) != new[os.path.basename(o)]:
             jobs.append([hipcc, *flags, "-c", s, "-o", o])
 

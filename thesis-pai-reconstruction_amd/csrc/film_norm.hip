@@ -10,6 +10,8 @@
 //                          finalize  the slabs summed in fp64 in a fixed order; demb, dgamma +=, dbeta +=, dbeta / M, dgamma / M
 //                          apply     dx = gamma rstd (du (1 + s) - dbeta / M - xhat dgamma / M)
 //                        No atomics, no sum across workgroups in arrival order: the same bits on every run.
+//   pai_film_norm_fwd_rng, pai_film_norm_bwd_rng    the same kernel bodies with the keep flags m formed from a Philox block per
+//                        vector (philox.h) instead of read from a mask: no mask tensor exists, the backward rebuilds the flags.
 //
 // All three tensor kernels share one geometry: C = 8 G, a thread keeps the channel group tid % G and the row lane tid / G
 // of the R = 256 / G rows a workgroup covers at a time (threads past R * G idle), builds its coefficients once and has FV
@@ -17,6 +19,7 @@
 // [slab * rps, (slab + 1) * rps) of sample n, rps = ceil(rows / slabs); a slab past the last row owns nothing, and in the
 // reduce it still writes its (zero) partial sums, so the finalize never reads what no launch wrote.
 #include "common.h"
+#include "philox.h"
 
 #include <math.h>
 
@@ -64,6 +67,25 @@ __device__ __forceinline__ float fn_mk(uint2 v, int e, float ks) {
     return (((e < 4 ? v.x : v.y) >> (8 * (e & 3))) & 0xffu) ? ks : 0.f;
 }
 
+// Where the eight keep flags of a vector come from: a uint8 mask in memory (pai_film_norm_fwd / _bwd), or one Philox block of
+// (seed, stream, step) per vector (the _rng forms; philox.h) -- integer work that has no operand from memory, so it runs while
+// the vector loads issued in front of it are in flight.  `off` is the flat element offset of the vector, a multiple of 8.
+struct FnMaskSrc {
+    const unsigned char* mask;
+    bool aligned() const { return ((uintptr_t)mask) % 8 == 0; }
+    __device__ __forceinline__ bool on() const { return mask != nullptr; }
+    __device__ __forceinline__ uint2 operator()(int64_t off) const { return fn_mask_ld(mask, off); }
+};
+struct FnRngSrc {
+    PhiloxKey key;
+    uint32_t thr;
+    bool aligned() const { return true; }
+    __device__ __forceinline__ bool on() const { return true; }
+    __device__ __forceinline__ uint2 operator()(int64_t off) const {
+        return philox_keep8(philox_block(key, (uint32_t)(off >> 3)), thr);
+    }
+};
+
 struct FnRows {
     int64_t r0, r1;                    // rows of this workgroup
 };
@@ -73,14 +95,14 @@ __device__ __forceinline__ FnRows fn_rows(int64_t rows) {
     return {r0, min(rows, r0 + rps)};
 }
 
-template <typename T, int ACT>
+template <typename T, int ACT, typename KS>
 __global__ __launch_bounds__(256) void film_norm_fwd_k(const T* x, int64_t rows, int G, int R, const float* mean, const float* rstd,
                                                        const float* gamma, const float* beta, const T* emb, int64_t ld,
-                                                       const unsigned char* mask, float keep_scale, T* out) {
+                                                       KS keep, float keep_scale, T* out) {
     const int cg = threadIdx.x % G, rr = threadIdx.x / G;
     if (rr >= R) return;
     const int C = G * 8, n = blockIdx.y;
-    const float ks = mask ? keep_scale : 1.f;
+    const float ks = keep.on() ? keep_scale : 1.f;
     float mu[8], rs[8], a[8], b[8], sc[8];
     V8<float>::ld(mean + cg * 8, mu);
     V8<float>::ld(rstd + cg * 8, rs);
@@ -95,7 +117,7 @@ __global__ __launch_bounds__(256) void film_norm_fwd_k(const T* x, int64_t rows,
             const int64_t r = rb + (int64_t)k * R;
             if (r < w.r1) {
                 V8<T>::ld(x + base + r * C, v[k]);
-                mv[k] = fn_mask_ld(mask, base + r * C);
+                mv[k] = keep(base + r * C);
             }
         }
 #pragma unroll
@@ -114,15 +136,15 @@ __global__ __launch_bounds__(256) void film_norm_fwd_k(const T* x, int64_t rows,
 }
 
 // ws: [N][slabs][2][C] partial (S0, S1), then [2][C] = (dbeta / M, dgamma / M)
-template <typename T, int ACT>
+template <typename T, int ACT, typename KS>
 __global__ __launch_bounds__(256) void film_norm_bwd_reduce_k(const T* g, const T* x, int64_t rows, int G, int R, const float* mean,
                                                               const float* rstd, const float* gamma, const float* beta,
-                                                              const T* emb, int64_t ld, const unsigned char* mask,
-                                                              float keep_scale, float* ws) {
+                                                              const T* emb, int64_t ld, KS keep, float keep_scale,
+                                                              float* ws) {
     __shared__ __attribute__((aligned(16))) float red[2][256 * 8];
     const int cg = threadIdx.x % G, rr = threadIdx.x / G;
     const int C = G * 8, n = blockIdx.y;
-    const float ks = mask ? keep_scale : 1.f;
+    const float ks = keep.on() ? keep_scale : 1.f;
     float s0[8], s1[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) s0[e] = s1[e] = 0.f;
@@ -142,7 +164,7 @@ __global__ __launch_bounds__(256) void film_norm_bwd_reduce_k(const T* g, const 
                 if (r < w.r1) {
                     V8<T>::ld(x + base + r * C, v[k]);
                     V8<T>::ld(g + base + r * C, gv[k]);
-                    mv[k] = fn_mask_ld(mask, base + r * C);
+                    mv[k] = keep(base + r * C);
                 }
             }
 #pragma unroll
@@ -231,15 +253,15 @@ __global__ __launch_bounds__(1024) void film_norm_bwd_finalize_k(float* ws, int 
 }
 
 // dx = du p - q - xhat w with p = gamma (1 + s) rstd, q = gamma rstd dbeta / M, w = gamma rstd dgamma / M
-template <typename T, int ACT>
+template <typename T, int ACT, typename KS>
 __global__ __launch_bounds__(256) void film_norm_bwd_apply_k(const T* g, const T* x, int64_t rows, int G, int R, const float* mean,
                                                              const float* rstd, const float* gamma, const float* beta,
-                                                             const T* emb, int64_t ld, const unsigned char* mask,
-                                                             float keep_scale, const float* tail, T* dx) {
+                                                             const T* emb, int64_t ld, KS keep, float keep_scale,
+                                                             const float* tail, T* dx) {
     const int cg = threadIdx.x % G, rr = threadIdx.x / G;
     if (rr >= R) return;
     const int C = G * 8, n = blockIdx.y;
-    const float ks = mask ? keep_scale : 1.f;
+    const float ks = keep.on() ? keep_scale : 1.f;
     float mu[8], rs[8], a[8], b[8], p[8], qv[8], wv[8];
     V8<float>::ld(mean + cg * 8, mu);
     V8<float>::ld(rstd + cg * 8, rs);
@@ -266,7 +288,7 @@ __global__ __launch_bounds__(256) void film_norm_bwd_apply_k(const T* g, const T
             if (r < w.r1) {
                 V8<T>::ld(x + base + r * C, v[k]);
                 V8<T>::ld(g + base + r * C, gv[k]);
-                mv[k] = fn_mask_ld(mask, base + r * C);
+                mv[k] = keep(base + r * C);
             }
         }
 #pragma unroll
@@ -304,20 +326,22 @@ static int film_norm_check(const char* who, int dtype, int64_t rows, int N, int 
     return 0;
 }
 
-extern "C" int pai_film_norm_fwd(int dtype, const void* x, int64_t rows, int N, int C, const float* mean, const float* rstd,
-                                 const float* gamma, const float* beta, const void* emb, int64_t ld, const unsigned char* mask,
-                                 float keep_scale, int act, void* out, void* stream) {
-    if (film_norm_check("pai_film_norm_fwd", dtype, rows, N, C, emb, ld, act)) return 1;
-    PAI_CHECK(x && mean && rstd && gamma && beta && out, "pai_film_norm_fwd: null tensor");
+// The launches of both forms: `keep` is the mask pointer or the Philox tuple; the caller has checked what is its own.
+template <typename KS>
+static int film_norm_fwd_launch(const char* who, int dtype, const void* x, int64_t rows, int N, int C, const float* mean,
+                                const float* rstd, const float* gamma, const float* beta, const void* emb, int64_t ld, KS keep,
+                                float keep_scale, int act, void* out, void* stream) {
+    if (film_norm_check(who, dtype, rows, N, C, emb, ld, act)) return 1;
+    PAI_CHECK(x && mean && rstd && gamma && beta && out, "%s: null tensor", who);
     PAI_CHECK((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)mean) | ((uintptr_t)rstd) | ((uintptr_t)gamma) | ((uintptr_t)beta)) % 16 == 0 &&
-                  ((uintptr_t)mask) % 8 == 0,
-              "pai_film_norm_fwd: tensors must be 16-byte aligned (the mask 8-byte)");
+                  keep.aligned(),
+              "%s: tensors must be 16-byte aligned (the mask 8-byte)", who);
     const int G = C / 8, R = 256 / G;
     const dim3 grid(pai_film_norm_slabs(rows), N);
     hipStream_t s = (hipStream_t)stream;
-#define PAI_FN_FWD(TT, ACT)                                                                                                    \
-    hipLaunchKernelGGL((film_norm_fwd_k<TT, ACT>), grid, dim3(256), 0, s, (const TT*)x, rows, G, R, mean, rstd, gamma, beta, \
-                       (const TT*)emb, ld, mask, keep_scale, (TT*)out)
+#define PAI_FN_FWD(TT, ACT)                                                                                                        \
+    hipLaunchKernelGGL((film_norm_fwd_k<TT, ACT, KS>), grid, dim3(256), 0, s, (const TT*)x, rows, G, R, mean, rstd, gamma, beta, \
+                       (const TT*)emb, ld, keep, keep_scale, (TT*)out)
     if (dtype == PAI_F32) {
         if (act == PAI_ACT_SILU) PAI_FN_FWD(float, PAI_ACT_SILU); else PAI_FN_FWD(float, PAI_ACT_NONE);
     } else {
@@ -328,28 +352,29 @@ extern "C" int pai_film_norm_fwd(int dtype, const void* x, int64_t rows, int N, 
     return 0;
 }
 
-extern "C" int pai_film_norm_bwd(int dtype, const void* g, const void* x, int64_t rows, int N, int C, const float* mean,
-                                 const float* rstd, const float* gamma, const float* beta, const void* emb, int64_t ld,
-                                 const unsigned char* mask, float keep_scale, int act, void* dx, void* demb, float* dgamma,
-                                 float* dbeta, float* ws, void* stream) {
-    if (film_norm_check("pai_film_norm_bwd", dtype, rows, N, C, emb, ld, act)) return 1;
-    PAI_CHECK(g && x && mean && rstd && gamma && beta && dx && ws, "pai_film_norm_bwd: null tensor");
-    PAI_CHECK(!emb || demb, "pai_film_norm_bwd: emb without demb");
+template <typename KS>
+static int film_norm_bwd_launch(const char* who, int dtype, const void* g, const void* x, int64_t rows, int N, int C,
+                                const float* mean, const float* rstd, const float* gamma, const float* beta, const void* emb,
+                                int64_t ld, KS keep, float keep_scale, int act, void* dx, void* demb, float* dgamma, float* dbeta,
+                                float* ws, void* stream) {
+    if (film_norm_check(who, dtype, rows, N, C, emb, ld, act)) return 1;
+    PAI_CHECK(g && x && mean && rstd && gamma && beta && dx && ws, "%s: null tensor", who);
+    PAI_CHECK(!emb || demb, "%s: emb without demb", who);
     PAI_CHECK((((uintptr_t)g) | ((uintptr_t)x) | ((uintptr_t)dx) | ((uintptr_t)ws) | ((uintptr_t)mean) | ((uintptr_t)rstd) |
-               ((uintptr_t)gamma) | ((uintptr_t)beta)) % 16 == 0 && ((uintptr_t)mask) % 8 == 0,
-              "pai_film_norm_bwd: tensors must be 16-byte aligned (the mask 8-byte)");
+               ((uintptr_t)gamma) | ((uintptr_t)beta)) % 16 == 0 && keep.aligned(),
+              "%s: tensors must be 16-byte aligned (the mask 8-byte)", who);
     const int G = C / 8, R = 256 / G, slabs = pai_film_norm_slabs(rows);
     const dim3 grid(slabs, N);
     float* tail = ws + (int64_t)N * slabs * 2 * C;
     const double inv_m = 1.0 / ((double)N * (double)rows);
     hipStream_t s = (hipStream_t)stream;
 #define PAI_FN_BWD(TT, ACT)                                                                                                        \
-    hipLaunchKernelGGL((film_norm_bwd_reduce_k<TT, ACT>), grid, dim3(256), 0, s, (const TT*)g, (const TT*)x, rows, G, R, mean,    \
-                       rstd, gamma, beta, (const TT*)emb, ld, mask, keep_scale, ws);                                               \
+    hipLaunchKernelGGL((film_norm_bwd_reduce_k<TT, ACT, KS>), grid, dim3(256), 0, s, (const TT*)g, (const TT*)x, rows, G, R, mean, \
+                       rstd, gamma, beta, (const TT*)emb, ld, keep, keep_scale, ws);                                               \
     hipLaunchKernelGGL((film_norm_bwd_finalize_k<TT>), dim3(C / 8), dim3(1024), 0, s, ws, N, slabs, C, inv_m, gamma, beta,        \
                        (const TT*)emb, ld, (TT*)demb, dgamma, dbeta);                                                              \
-    hipLaunchKernelGGL((film_norm_bwd_apply_k<TT, ACT>), grid, dim3(256), 0, s, (const TT*)g, (const TT*)x, rows, G, R, mean,     \
-                       rstd, gamma, beta, (const TT*)emb, ld, mask, keep_scale, (const float*)tail, (TT*)dx)
+    hipLaunchKernelGGL((film_norm_bwd_apply_k<TT, ACT, KS>), grid, dim3(256), 0, s, (const TT*)g, (const TT*)x, rows, G, R, mean,  \
+                       rstd, gamma, beta, (const TT*)emb, ld, keep, keep_scale, (const float*)tail, (TT*)dx)
     if (dtype == PAI_F32) {
         if (act == PAI_ACT_SILU) { PAI_FN_BWD(float, PAI_ACT_SILU); } else { PAI_FN_BWD(float, PAI_ACT_NONE); }
     } else {
@@ -358,4 +383,45 @@ extern "C" int pai_film_norm_bwd(int dtype, const void* g, const void* x, int64_
 #undef PAI_FN_BWD
     PAI_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int pai_film_norm_fwd(int dtype, const void* x, int64_t rows, int N, int C, const float* mean, const float* rstd,
+                                 const float* gamma, const float* beta, const void* emb, int64_t ld, const unsigned char* mask,
+                                 float keep_scale, int act, void* out, void* stream) {
+    return film_norm_fwd_launch("pai_film_norm_fwd", dtype, x, rows, N, C, mean, rstd, gamma, beta, emb, ld, FnMaskSrc{mask},
+                                keep_scale, act, out, stream);
+}
+
+extern "C" int pai_film_norm_bwd(int dtype, const void* g, const void* x, int64_t rows, int N, int C, const float* mean,
+                                 const float* rstd, const float* gamma, const float* beta, const void* emb, int64_t ld,
+                                 const unsigned char* mask, float keep_scale, int act, void* dx, void* demb, float* dgamma,
+                                 float* dbeta, float* ws, void* stream) {
+    return film_norm_bwd_launch("pai_film_norm_bwd", dtype, g, x, rows, N, C, mean, rstd, gamma, beta, emb, ld, FnMaskSrc{mask},
+                                keep_scale, act, dx, demb, dgamma, dbeta, ws, stream);
+}
+
+// The Philox forms: one block per vector of eight elements, block = flat offset / 8 (philox.h).
+static int film_norm_rng_check(const char* who, int64_t rows, int N, int C, uint32_t thr) {
+    PAI_CHECK(thr <= 65536u, "%s: thr=%u (round(p 65536), at most 65536)", who, thr);
+    PAI_CHECK(N < 1 || rows < 1 || C < 8 || rows <= ((1ll << 35) / C) / N, "%s: tensor too large (more than 2^32 blocks of 8)", who);
+    return 0;
+}
+
+extern "C" int pai_film_norm_fwd_rng(int dtype, const void* x, int64_t rows, int N, int C, const float* mean, const float* rstd,
+                                     const float* gamma, const float* beta, const void* emb, int64_t ld, uint64_t seed,
+                                     uint32_t stream, uint32_t step, uint32_t thr, float keep_scale, int act, void* out,
+                                     void* stream_handle) {
+    if (film_norm_rng_check("pai_film_norm_fwd_rng", rows, N, C, thr)) return 1;
+    return film_norm_fwd_launch("pai_film_norm_fwd_rng", dtype, x, rows, N, C, mean, rstd, gamma, beta, emb, ld,
+                                FnRngSrc{philox_key(seed, 0, stream, step), thr}, keep_scale, act, out, stream_handle);
+}
+
+extern "C" int pai_film_norm_bwd_rng(int dtype, const void* g, const void* x, int64_t rows, int N, int C, const float* mean,
+                                     const float* rstd, const float* gamma, const float* beta, const void* emb, int64_t ld,
+                                     uint64_t seed, uint32_t stream, uint32_t step, uint32_t thr, float keep_scale, int act,
+                                     void* dx, void* demb, float* dgamma, float* dbeta, float* ws, void* stream_handle) {
+    if (film_norm_rng_check("pai_film_norm_bwd_rng", rows, N, C, thr)) return 1;
+    return film_norm_bwd_launch("pai_film_norm_bwd_rng", dtype, g, x, rows, N, C, mean, rstd, gamma, beta, emb, ld,
+                                FnRngSrc{philox_key(seed, 0, stream, step), thr}, keep_scale, act, dx, demb, dgamma, dbeta, ws,
+                                stream_handle);
 }

@@ -25,10 +25,12 @@
 //   pai_gamma_embedding  [cos(g f_i) | sin(g f_i)] (nn.py:140-157).
 //   pai_palette_step     one reverse diffusion step, elementwise (palette.py:233-306).
 //   pai_palette_noise    the forward noising q(y_t | y_0) with t, gammas and gammas_prev on the device (palette.py:214-231; training).
+//   pai_palette_step_rng, pai_palette_noise_rng  the same two kernels with their random numbers drawn inside (philox.h).
 //   pai_palette_objective  the MSE + variational-bound loss and its gradient into the U-Net output (palette.py:122-140, 254-333,
 //                        368-427; training): a pass over (slab, sample) workgroups with fp64 partial sums, then one workgroup
 //                        that adds them in a fixed order.
 #include "common.h"
+#include "philox.h"
 
 #include <math.h>
 
@@ -1034,9 +1036,10 @@ extern "C" int pai_gamma_embedding(int dtype, const float* gammas, int N, int di
 // y0 = clamp((y_t - s1 eps) rs, -1, 1); mean = c0 y0 + c1 y_t; log variance = v log_hi + (1 - v) log_lo with v = (var + 1) / 2
 // (learn_var) or log_lo; y_{t-1} = mean + exp(0.5 log variance) noise (add_noise) -- the expression order of
 // palette.py:233-306.  Pixels are [pixel][channel]; the model output has C (or, learn_var, 2 C: eps | var) columns.
-template <typename T>
-__global__ __launch_bounds__(256) void palette_step_k(const T* mo, const float* y_t, const float* noise, int64_t numel, int C,
-                                                      int learn_var, int add_noise, float s1, float rs, float c0, float c1,
+// RNG: the noise of element i is normal i of the Philox tuple `key` (stream 3, sub = the draw index), not noise[i].
+template <typename T, bool RNG>
+__global__ __launch_bounds__(256) void palette_step_k(const T* mo, const float* y_t, const float* noise, PhiloxKey key, int64_t numel,
+                                                      int C, int learn_var, int add_noise, float s1, float rs, float c0, float c1,
                                                       float log_lo, float log_hi, float* y_next, T* xy_next) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= numel) return;
@@ -1053,58 +1056,104 @@ __global__ __launch_bounds__(256) void palette_step_k(const T* mo, const float* 
         const float vi = (Conv<T>::ld(mo + px * Cm + C + c) + 1.f) * 0.5f;
         lv = vi * log_hi + (1.f - vi) * log_lo;
     }
-    const float out = add_noise ? mean + expf(0.5f * lv) * noise[i] : mean;
+    float z = 0.f;
+    if (add_noise) z = RNG ? philox_normal_at(key, i) : noise[i];
+    const float out = add_noise ? mean + expf(0.5f * lv) * z : mean;
     y_next[i] = out;
     if (xy_next) Conv<T>::st(xy_next + px * 2 * C + C + c, out);
+}
+
+template <bool RNG>
+static int palette_step_launch(const char* who, int dtype, const void* model_out, const float* y_t, const float* noise, PhiloxKey key,
+                               int64_t pixels, int C, int learn_var, int add_noise, float s1, float rs, float c0, float c1,
+                               float log_lo, float log_hi, float* y_next, void* xy_next, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "%s: dtype=%d", who, dtype);
+    PAI_CHECK(model_out && y_t && y_next && (RNG || noise || !add_noise), "%s: null tensor", who);
+    PAI_CHECK(pixels >= 1 && C >= 1, "%s: pixels=%lld C=%d", who, (long long)pixels, C);
+    PAI_CHECK(!RNG || pixels <= (1ll << 34) / C, "%s: tensor too large (more than 2^32 blocks of 4)", who);
+    const int64_t numel = pixels * C;
+    PAI_CHECK((numel + 255) / 256 < (1ll << 31), "%s: tensor too large", who);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((numel + 255) / 256));
+    if (dtype == PAI_F32)
+        hipLaunchKernelGGL((palette_step_k<float, RNG>), grid, dim3(256), 0, s, (const float*)model_out, y_t, noise, key, numel, C,
+                           learn_var, add_noise, s1, rs, c0, c1, log_lo, log_hi, y_next, (float*)xy_next);
+    else
+        hipLaunchKernelGGL((palette_step_k<bf16_t, RNG>), grid, dim3(256), 0, s, (const bf16_t*)model_out, y_t, noise, key, numel, C,
+                           learn_var, add_noise, s1, rs, c0, c1, log_lo, log_hi, y_next, (bf16_t*)xy_next);
+    PAI_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int pai_palette_step(int dtype, const void* model_out, const float* y_t, const float* noise, int64_t pixels, int C,
                                 int learn_var, int add_noise, float s1, float rs, float c0, float c1, float log_lo, float log_hi,
                                 float* y_next, void* xy_next, void* stream) {
-    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_palette_step: dtype=%d", dtype);
-    PAI_CHECK(model_out && y_t && y_next && (noise || !add_noise), "pai_palette_step: null tensor");
-    PAI_CHECK(pixels >= 1 && C >= 1, "pai_palette_step: pixels=%lld C=%d", (long long)pixels, C);
-    const int64_t numel = pixels * C;
-    PAI_CHECK((numel + 255) / 256 < (1ll << 31), "pai_palette_step: tensor too large");
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((numel + 255) / 256));
-    if (dtype == PAI_F32)
-        hipLaunchKernelGGL(palette_step_k<float>, grid, dim3(256), 0, s, (const float*)model_out, y_t, noise, numel, C, learn_var,
-                           add_noise, s1, rs, c0, c1, log_lo, log_hi, y_next, (float*)xy_next);
-    else
-        hipLaunchKernelGGL(palette_step_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)model_out, y_t, noise, numel, C, learn_var,
-                           add_noise, s1, rs, c0, c1, log_lo, log_hi, y_next, (bf16_t*)xy_next);
-    PAI_LAUNCH_CHECK();
-    return 0;
+    return palette_step_launch<false>("pai_palette_step", dtype, model_out, y_t, noise, PhiloxKey{}, pixels, C, learn_var, add_noise,
+                                      s1, rs, c0, c1, log_lo, log_hi, y_next, xy_next, stream);
+}
+
+extern "C" int pai_palette_step_rng(int dtype, const void* model_out, const float* y_t, int64_t pixels, int C, int learn_var,
+                                    int add_noise, float s1, float rs, float c0, float c1, float log_lo, float log_hi,
+                                    uint64_t seed, uint32_t sub, uint32_t step, float* y_next, void* xy_next, void* stream_handle) {
+    return palette_step_launch<true>("pai_palette_step_rng", dtype, model_out, y_t, nullptr,
+                                     philox_key(seed, sub, PHILOX_STREAM_SAMPLER, step), pixels, C, learn_var, add_noise, s1, rs, c0,
+                                     c1, log_lo, log_hi, y_next, xy_next, stream_handle);
 }
 
 // ---- forward noising q(y_t | y_0) ----------------------------------------------------------------------------------------------------
 // gamma = (gammas[t] - gammas_prev[t]) u + gammas_prev[t], noise = z (t > 0), y_t = sqrt(gamma) y0 + sqrt(1 - gamma) noise
 // (palette.py:214-231).  Grid (chunks, N): sample n reads its t, clamped into the table, once.  VEC: 4 | P C, a thread owns one
 // 16-byte vector of each tensor; otherwise one element.  The thread (0, 0) of a sample writes gamma[n].
-template <bool VEC>
-__global__ __launch_bounds__(256) void palette_noise_k(const float* y0, const float* z, const float* u, const int* t,
-                                                       const float* gammas, const float* gammas_prev, int T, int64_t PC, float* y_t,
-                                                       float* noise, float* gamma) {
+// RNG: t[n], u[n] and z are drawn here (philox.h: integer n of stream 0, uniform n of stream 1, the normals of stream 2 over the
+// flat [N][P][C] tensor); every workgroup of sample n recomputes t and u, the thread (0, 0) of the sample writes t[n].
+template <bool VEC, bool RNG>
+__global__ __launch_bounds__(256) void palette_noise_k(const float* y0, const float* z, const float* u, const int* t, PhiloxKey key,
+                                                       int* t_out, const float* gammas, const float* gammas_prev, int T, int64_t PC,
+                                                       float* y_t, float* noise, float* gamma) {
     const int n = blockIdx.y;
-    const int tc = min(max(t[n], 0), T - 1);
+    int tn;
+    float un;
+    if (RNG) {
+        PhiloxKey kt = key, ku = key;
+        kt.stream = PHILOX_STREAM_T;
+        ku.stream = PHILOX_STREAM_U;
+        const PhiloxBlock bt = philox_block(kt, (uint32_t)n >> 2), bu = philox_block(ku, (uint32_t)n >> 2);
+        const int l = n & 3;
+        tn = philox_int(l == 0 ? bt.w[0] : l == 1 ? bt.w[1] : l == 2 ? bt.w[2] : bt.w[3], (uint32_t)T);
+        un = philox_uniform(l == 0 ? bu.w[0] : l == 1 ? bu.w[1] : l == 2 ? bu.w[2] : bu.w[3]);
+    } else {
+        tn = t[n];
+        un = u[n];
+    }
+    const int tc = min(max(tn, 0), T - 1);
     const float gp = gammas_prev[tc];
-    const float g = fmaf(gammas[tc] - gp, u[n], gp);
+    const float g = fmaf(gammas[tc] - gp, un, gp);
     const float keep = tc > 0 ? 1.f : 0.f;             // the product z * 0 keeps the sign of z, as torch's z * (t > 0)
     const float sg = sqrtf(g), s1 = sqrtf(1.f - g);
-    if (blockIdx.x == 0 && threadIdx.x == 0) gamma[n] = g;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        gamma[n] = g;
+        if (RNG) t_out[n] = tn;
+    }
     const int64_t base = (int64_t)n * PC;
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
     if (i >= PC) return;
     if (VEC) {
-        const float4 a = *(const float4*)(y0 + base + i), b = *(const float4*)(z + base + i);
+        const float4 a = *(const float4*)(y0 + base + i);
+        float4 b;
+        if (RNG) {
+            float zz[4];
+            philox_normal4(philox_block(key, (uint32_t)((base + i) >> 2)), zz);       // 4 | P C: base + i is a multiple of 4
+            b = make_float4(zz[0], zz[1], zz[2], zz[3]);
+        } else {
+            b = *(const float4*)(z + base + i);
+        }
         float4 e, y;
         e.x = b.x * keep, e.y = b.y * keep, e.z = b.z * keep, e.w = b.w * keep;
         y.x = fmaf(sg, a.x, s1 * e.x), y.y = fmaf(sg, a.y, s1 * e.y), y.z = fmaf(sg, a.z, s1 * e.z), y.w = fmaf(sg, a.w, s1 * e.w);
         *(float4*)(noise + base + i) = e;
         *(float4*)(y_t + base + i) = y;
     } else {
-        const float e = z[base + i] * keep;
+        const float e = (RNG ? philox_normal_at(key, base + i) : z[base + i]) * keep;
         noise[base + i] = e;
         y_t[base + i] = fmaf(sg, y0[base + i], s1 * e);
     }
@@ -1112,29 +1161,48 @@ __global__ __launch_bounds__(256) void palette_noise_k(const float* y0, const fl
 
 #define PAI_ALIGNED16(p) (((uintptr_t)(p) & 15) == 0)
 
-extern "C" int pai_palette_noise(const float* y0, const float* z, const float* u, const int32_t* t, const float* gammas,
-                                 const float* gammas_prev, int T, int N, int64_t P, int C, float* y_t, float* noise, float* gamma,
-                                 void* stream) {
-    PAI_CHECK(y0 && z && u && t && gammas && gammas_prev && y_t && noise && gamma, "pai_palette_noise: null tensor");
-    PAI_CHECK(N >= 1 && P >= 1, "pai_palette_noise: N=%d P=%lld", N, (long long)P);
-    PAI_CHECK(C >= 1 && C <= 4, "pai_palette_noise: C=%d (1..4)", C);
-    PAI_CHECK(T >= 1, "pai_palette_noise: T=%d", T);
-    PAI_CHECK(PAI_ALIGNED16(y0) && PAI_ALIGNED16(z) && PAI_ALIGNED16(u) && PAI_ALIGNED16(t) && PAI_ALIGNED16(gammas) &&
-                  PAI_ALIGNED16(gammas_prev) && PAI_ALIGNED16(y_t) && PAI_ALIGNED16(noise) && PAI_ALIGNED16(gamma),
-              "pai_palette_noise: tensors must be 16-byte aligned");
-    PAI_CHECK(N <= 65535 && P <= (1ll << 40), "pai_palette_noise: tensor too large (N=%d P=%lld)", N, (long long)P);
+template <bool RNG>
+static int palette_noise_launch(const char* who, const float* y0, const float* z, const float* u, const int32_t* t, PhiloxKey key,
+                                int32_t* t_out, const float* gammas, const float* gammas_prev, int T, int N, int64_t P, int C,
+                                float* y_t, float* noise, float* gamma, void* stream) {
+    PAI_CHECK(y0 && (RNG ? t_out != nullptr : (z && u && t)) && gammas && gammas_prev && y_t && noise && gamma, "%s: null tensor", who);
+    PAI_CHECK(N >= 1 && P >= 1, "%s: N=%d P=%lld", who, N, (long long)P);
+    PAI_CHECK(C >= 1 && C <= 4, "%s: C=%d (1..4)", who, C);
+    PAI_CHECK(T >= 1, "%s: T=%d", who, T);
+    PAI_CHECK(PAI_ALIGNED16(y0) && PAI_ALIGNED16(z) && PAI_ALIGNED16(u) && PAI_ALIGNED16(t) && PAI_ALIGNED16(t_out) &&
+                  PAI_ALIGNED16(gammas) && PAI_ALIGNED16(gammas_prev) && PAI_ALIGNED16(y_t) && PAI_ALIGNED16(noise) &&
+                  PAI_ALIGNED16(gamma),
+              "%s: tensors must be 16-byte aligned", who);
+    PAI_CHECK(N <= 65535 && P <= (1ll << 40), "%s: tensor too large (N=%d P=%lld)", who, N, (long long)P);
     const int64_t PC = P * C;
     const bool vec = PC % 4 == 0;
     const int64_t chunks = ((vec ? PC / 4 : PC) + 255) / 256;
-    PAI_CHECK(chunks < (1ll << 31) && PC <= (1ll << 62) / N, "pai_palette_noise: tensor too large");
+    PAI_CHECK(chunks < (1ll << 31) && PC <= (1ll << 62) / N, "%s: tensor too large", who);
+    PAI_CHECK(!RNG || (PC * N + 3) / 4 <= (1ll << 32), "%s: tensor too large (more than 2^32 blocks of 4)", who);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)chunks, (unsigned)N);
     if (vec)
-        hipLaunchKernelGGL(palette_noise_k<true>, grid, dim3(256), 0, s, y0, z, u, t, gammas, gammas_prev, T, PC, y_t, noise, gamma);
+        hipLaunchKernelGGL((palette_noise_k<true, RNG>), grid, dim3(256), 0, s, y0, z, u, t, key, t_out, gammas, gammas_prev, T, PC,
+                           y_t, noise, gamma);
     else
-        hipLaunchKernelGGL(palette_noise_k<false>, grid, dim3(256), 0, s, y0, z, u, t, gammas, gammas_prev, T, PC, y_t, noise, gamma);
+        hipLaunchKernelGGL((palette_noise_k<false, RNG>), grid, dim3(256), 0, s, y0, z, u, t, key, t_out, gammas, gammas_prev, T, PC,
+                           y_t, noise, gamma);
     PAI_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int pai_palette_noise(const float* y0, const float* z, const float* u, const int32_t* t, const float* gammas,
+                                 const float* gammas_prev, int T, int N, int64_t P, int C, float* y_t, float* noise, float* gamma,
+                                 void* stream) {
+    return palette_noise_launch<false>("pai_palette_noise", y0, z, u, t, PhiloxKey{}, nullptr, gammas, gammas_prev, T, N, P, C, y_t,
+                                       noise, gamma, stream);
+}
+
+extern "C" int pai_palette_noise_rng(const float* y0, const float* gammas, const float* gammas_prev, int T, int N, int64_t P, int C,
+                                     uint64_t seed, uint32_t step, int32_t* t, float* y_t, float* noise, float* gamma,
+                                     void* stream_handle) {
+    return palette_noise_launch<true>("pai_palette_noise_rng", y0, nullptr, nullptr, nullptr, philox_key(seed, 0, PHILOX_STREAM_Z, step),
+                                      t, gammas, gammas_prev, T, N, P, C, y_t, noise, gamma, stream_handle);
 }
 
 // ---- MSE + variational bound and the gradient into the U-Net output -----------------------------------------------------------

@@ -1,0 +1,74 @@
+// pai_philox_fill: the generator of philox.h written out as a tensor -- the surface its bits are pinned through, and a utility
+// (the sampler's y_T).  A thread owns one block: four elements (raw, uniform, normal, integer) or eight (keep), stored as one
+// vector where the whole block lies below n and `out` is aligned for it, element by element otherwise.
+#include "common.h"
+#include "philox.h"
+
+template <int KIND>
+__global__ __launch_bounds__(256) void philox_fill_k(void* out, int64_t n, PhiloxKey key, uint32_t param, int vec) {
+    constexpr int E = KIND == PAI_PHILOX_KEEP ? 8 : 4;
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i0 = b * E;
+    if (i0 >= n) return;
+    const PhiloxBlock blk = philox_block(key, (uint32_t)b);
+    const bool whole = vec && i0 + E <= n;
+    if (KIND == PAI_PHILOX_KEEP) {
+        const uint2 v = philox_keep8(blk, param);
+        unsigned char* o = (unsigned char*)out;
+        if (whole) {
+            *(uint2*)(o + i0) = v;
+        } else {
+            for (int e = 0; e < 8 && i0 + e < n; ++e) o[i0 + e] = (unsigned char)(((e < 4 ? v.x : v.y) >> (8 * (e & 3))) & 0xffu);
+        }
+        return;
+    }
+    uint32_t w[4];                                 // the four elements as their bit patterns
+    if (KIND == PAI_PHILOX_NORMAL) {
+        float z[4];
+        philox_normal4(blk, z);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[e] = __float_as_uint(z[e]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            w[e] = KIND == PAI_PHILOX_UNIFORM ? __float_as_uint(philox_uniform(blk.w[e]))
+                   : KIND == PAI_PHILOX_INT   ? (uint32_t)philox_int(blk.w[e], param)
+                                              : blk.w[e];
+    }
+    uint32_t* o = (uint32_t*)out;
+    if (whole) {
+        *(uint4*)(o + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (i0 + e < n) o[i0 + e] = w[e];
+    }
+}
+
+extern "C" int pai_philox_fill(int kind, void* out, int64_t n, uint64_t seed, uint32_t sub, uint32_t stream, uint32_t step,
+                               uint32_t param, void* stream_handle) {
+    PAI_CHECK(kind >= PAI_PHILOX_RAW && kind <= PAI_PHILOX_KEEP, "pai_philox_fill: kind=%d", kind);
+    PAI_CHECK(out, "pai_philox_fill: null tensor");
+    PAI_CHECK(n >= 1, "pai_philox_fill: n=%lld", (long long)n);
+    PAI_CHECK(kind != PAI_PHILOX_INT || (param >= 1 && param <= 0x7fffffffu), "pai_philox_fill: T=%u (1 .. 2^31 - 1)", param);
+    PAI_CHECK(kind != PAI_PHILOX_KEEP || param <= 65536u, "pai_philox_fill: thr=%u (round(p 65536), at most 65536)", param);
+    const int E = kind == PAI_PHILOX_KEEP ? 8 : 4, esz = kind == PAI_PHILOX_KEEP ? 1 : 4;
+    PAI_CHECK((uintptr_t)out % esz == 0, "pai_philox_fill: out is not aligned to its element type");
+    const int64_t blocks = (n - 1) / E + 1;
+    PAI_CHECK(blocks <= (1ll << 32), "pai_philox_fill: tensor too large (more than 2^32 blocks of %d)", E);
+    const int vec = (uintptr_t)out % (E * esz) == 0;
+    const dim3 grid((unsigned)((blocks + 255) / 256));
+    const PhiloxKey key = philox_key(seed, sub, stream, step);
+    hipStream_t s = (hipStream_t)stream_handle;
+#define PAI_PHILOX_FILL(K) hipLaunchKernelGGL(philox_fill_k<K>, grid, dim3(256), 0, s, out, n, key, param, vec)
+    switch (kind) {
+        case PAI_PHILOX_RAW: PAI_PHILOX_FILL(PAI_PHILOX_RAW); break;
+        case PAI_PHILOX_UNIFORM: PAI_PHILOX_FILL(PAI_PHILOX_UNIFORM); break;
+        case PAI_PHILOX_NORMAL: PAI_PHILOX_FILL(PAI_PHILOX_NORMAL); break;
+        case PAI_PHILOX_INT: PAI_PHILOX_FILL(PAI_PHILOX_INT); break;
+        default: PAI_PHILOX_FILL(PAI_PHILOX_KEEP); break;
+    }
+#undef PAI_PHILOX_FILL
+    PAI_LAUNCH_CHECK();
+    return 0;
+}

@@ -650,7 +650,7 @@ def spatial_attention(qkv, heads: int):
 class _FilmNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, emb_out, mask, keep_scale, act, running_mean, running_var, nbt, momentum, eps,
-                advance_in_backward=False):
+                advance_in_backward=False, rng=None):
         n, c = x.shape[0], x.shape[-1]
         rows = x[0].numel() // c
         m, dtype = n * rows, x.dtype
@@ -667,7 +667,10 @@ class _FilmNormAct(torch.autograd.Function):
                         shift)
         ld = emb_out.shape[1] if emb_out is not None else 0
         out = torch.empty_like(x)
-        ops.film_norm_fwd(dtype, x, rows, n, c, mean, rstd, gamma, beta, emb_out, ld, mask, keep_scale, act, out)
+        if rng is not None:                # (seed, stream, step, thr): the keep bits are formed in the kernel, no mask exists
+            ops.film_norm_fwd_rng(dtype, x, rows, n, c, mean, rstd, gamma, beta, emb_out, ld, *rng, keep_scale, act, out)
+        else:
+            ops.film_norm_fwd(dtype, x, rows, n, c, mean, rstd, gamma, beta, emb_out, ld, mask, keep_scale, act, out)
         # advance_in_backward: the reference runs this norm's forward a second time while it differentiates (its AttentionBlock
         # is always under gradient checkpointing), so the running buffers advance once more, on the same batch statistics, in
         # the backward pass.  The statistics are kept for that; nothing is recomputed.
@@ -676,6 +679,7 @@ class _FilmNormAct(torch.autograd.Function):
             ctx.again = (running_mean, running_var, nbt, srows, m, momentum, eps)
         ctx.save_for_backward(x, mean, rstd, gamma, beta, emb_out, mask, stats if ctx.again else None)
         ctx.dims = (n, rows, c, ld, keep_scale, act)
+        ctx.rng = rng
         return out
 
     @staticmethod
@@ -696,23 +700,32 @@ class _FilmNormAct(torch.autograd.Function):
         demb = torch.zeros_like(emb_out) if emb_out is not None else None
         dgb = torch.zeros(2 * c, **f32)
         ws = torch.empty(ops.film_norm_ws_floats(n, rows, c), **f32)
-        ops.film_norm_bwd(x.dtype, g.contiguous(), x, rows, n, c, mean, rstd, gamma, beta, emb_out, ld, mask, keep_scale, act, dx,
-                          demb, dgb[:c], dgb[c:], ws)
-        return (dx, dgb[:c], dgb[c:], demb) + (None,) * 9
+        if ctx.rng is not None:
+            ops.film_norm_bwd_rng(x.dtype, g.contiguous(), x, rows, n, c, mean, rstd, gamma, beta, emb_out, ld, *ctx.rng, keep_scale,
+                                  act, dx, demb, dgb[:c], dgb[c:], ws)
+        else:
+            ops.film_norm_bwd(x.dtype, g.contiguous(), x, rows, n, c, mean, rstd, gamma, beta, emb_out, ld, mask, keep_scale, act,
+                              dx, demb, dgb[:c], dgb[c:], ws)
+        return (dx, dgb[:c], dgb[c:], demb) + (None,) * 10
 
 
 def film_norm_act(x, weight, bias, emb_out=None, *, act="silu", dropout_mask=None, p=0.0, running_mean=None, running_var=None,
-                  num_batches_tracked=None, momentum=0.1, eps=1e-5, advance_in_backward=False):
+                  num_batches_tracked=None, momentum=0.1, eps=1e-5, advance_in_backward=False, dropout_rng=None):
     """A norm site of the guided-diffusion U-Net in training (reference models/guided_diffusion/unet.py:141-172,206-210):
     ``Dropout(act(BatchNorm(x) * (1 + scale) + shift))`` on batch statistics, with a backward.  x: [N, rows, C] or NHWC
     [N, H, W, C] (fp32 or bf16, contiguous, on the device); weight, bias: fp32 [C]; emb_out: None or [N, >= 2 C] of x's dtype with
     ``scale | shift`` in its first 2 C columns, contiguous (the output of ``emb_layers``); act: "silu" or "none";
     dropout_mask: uint8 of x's shape, 0 drops; with p > 0 and no mask one is drawn with ``torch.rand`` on the current stream.
+    dropout_rng = (seed, stream, step) instead of a mask: the keep bits are formed inside the kernels by the device generator
+    (csrc/philox.h; element kept iff its 16-bit lane >= round(p 65536)), the backward rebuilds them, no mask tensor exists and
+    torch's generator is not touched; with p = 0 nothing is dropped.  Not together with dropout_mask.
     running_mean / running_var / num_batches_tracked are updated in place as nn.BatchNorm does when they are given; with
     ``advance_in_backward`` they advance a second time, on the same batch statistics, when the backward pass runs (the
     reference's AttentionBlock norm, whose forward runs again under gradient checkpointing).  The
     forward keeps x, mean, rstd, emb_out and the mask, not its output; the backward returns the gradients of x, weight, bias
     and emb_out (``pai_film_norm_fwd`` / ``pai_film_norm_bwd``).  No host synchronisation."""
+    if dropout_rng is not None and dropout_mask is not None:
+        raise ops.PaiError("film_norm_act: dropout_rng and dropout_mask exclude each other")
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise ops.PaiError("film_norm_act needs a HIP device tensor (no CPU fallback exists)")
     if x.dim() not in (3, 4) or x.numel() == 0:
@@ -734,15 +747,22 @@ def film_norm_act(x, weight, bias, emb_out=None, *, act="silu", dropout_mask=Non
             raise ops.PaiError(f"film_norm_act: emb_out must be a contiguous [N, >= 2 C] tensor of {x.dtype}")
     if not 0.0 <= p < 1.0:
         raise ops.PaiError(f"film_norm_act: p={p}")
-    if dropout_mask is None and p > 0.0:
+    rng = None
+    if dropout_rng is not None:
+        if len(dropout_rng) != 3:
+            raise ops.PaiError("film_norm_act: dropout_rng is (seed, stream, step)")
+        if p > 0.0:
+            seed, stream, step = dropout_rng
+            rng = (ops._u64(seed), ops._u32(stream, "stream"), ops._u32(step, "step"), ops.dropout_thr(p))
+    elif dropout_mask is None and p > 0.0:
         dropout_mask = (torch.rand(x.shape, device=x.device) >= p).to(torch.uint8)
     if dropout_mask is not None and (dropout_mask.dtype != torch.uint8 or dropout_mask.shape != x.shape
                                      or not dropout_mask.is_contiguous()):
         raise ops.PaiError("film_norm_act: dropout_mask must be a contiguous uint8 tensor of x's shape")
-    keep_scale = 1.0 / (1.0 - p) if dropout_mask is not None else 1.0
+    keep_scale = 1.0 / (1.0 - p) if dropout_mask is not None or rng is not None else 1.0
     return _FilmNormAct.apply(x, weight, bias, emb_out, dropout_mask, keep_scale, ops.ACT_SILU if act == "silu" else ops.ACT_NONE,
                               running_mean, running_var, num_batches_tracked, float(momentum), float(eps),
-                              bool(advance_in_backward))
+                              bool(advance_in_backward), rng)
 
 
 # --------------------------------------------------------------------------------------
@@ -793,6 +813,51 @@ def palette_noise(y0, t, u, z, diffusion):
     gamma = torch.empty(n, dtype=torch.float32, device=p0.device)
     ops.palette_noise(p0, pz, u.reshape(-1).contiguous(), ti, g.contiguous(), gp.contiguous(), n, h * w, c, y_t, noise, gamma)
     return _nchw_view(y_t), _nchw_view(noise), gamma
+
+
+def palette_noise_rng(y0, seed, step, diffusion):
+    """``palette_noise`` with its three draws made inside the launch by the device generator (csrc/philox.h): t[n] = integer n
+    of stream 0 in [0, timesteps), u[n] = uniform n of stream 1, z = the normals of stream 2 over the NHWC pixels, all of the
+    tuple (seed, step).  y0 fp32 [N, C, H, W] -> (y_t, noise, gamma, t) with t int32 [N] on the device for ``palette_objective``;
+    one launch (``pai_palette_noise_rng``), torch's generator is not touched, nothing is copied to the host."""
+    p0 = _nhwc_pixels(y0, "palette_noise_rng")
+    n, h, w, c = p0.shape
+    if not 1 <= c <= 4:
+        raise ops.PaiError(f"palette_noise_rng: C={c} (1..4)")
+    g, gp = diffusion.gammas, diffusion.gammas_prev
+    if not g.is_cuda or g.device != p0.device:
+        raise ops.PaiError("palette_noise_rng: the schedule buffers are not on the device of y0 (move the model there)")
+    y_t, noise = torch.empty_like(p0), torch.empty_like(p0)
+    gamma = torch.empty(n, dtype=torch.float32, device=p0.device)
+    t = torch.empty(n, dtype=torch.int32, device=p0.device)
+    ops.palette_noise_rng(p0, g.contiguous(), gp.contiguous(), n, h * w, c, seed, step, t, y_t, noise, gamma)
+    return _nchw_view(y_t), _nchw_view(noise), gamma, t
+
+
+_PHILOX_KINDS = {"raw": ops.PHILOX_RAW, "uniform": ops.PHILOX_UNIFORM, "normal": ops.PHILOX_NORMAL, "int": ops.PHILOX_INT,
+                 "keep": ops.PHILOX_KEEP}
+
+
+def philox_fill(kind, shape, seed, sub=0, stream=0, step=0, param=0, device=None, out=None):
+    """A tensor of the device generator's values (csrc/philox.h, ``pai_philox_fill``): element i of the flat tensor is value i of
+    the tuple (seed, sub, stream, step).  kind: "raw" (the 32-bit words, as int32 bits), "uniform" (fp32 in [0, 1)), "normal"
+    (fp32), "int" (int32 in [0, param)), "keep" (uint8 0 / 1, kept iff the 16-bit lane >= param = round(p 65536)).  ``out``: a
+    contiguous device tensor of the kind's dtype to fill instead of a new one of ``shape`` on ``device``."""
+    if kind not in _PHILOX_KINDS:
+        raise ops.PaiError(f"philox_fill: kind={kind!r} (one of {sorted(_PHILOX_KINDS)})")
+    code = _PHILOX_KINDS[kind]
+    if out is None:
+        if device is None or torch.device(device).type != "cuda":
+            raise ops.PaiError("philox_fill needs a HIP device (no CPU fallback exists)")
+        out = torch.empty(shape, dtype=ops.PHILOX_DTYPES[code], device=device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda:
+        raise ops.PaiError("philox_fill needs a HIP device tensor (no CPU fallback exists)")
+    elif not out.is_contiguous() or out.dtype != ops.PHILOX_DTYPES[code]:
+        raise ops.PaiError(f"philox_fill: out must be a contiguous {ops.PHILOX_DTYPES[code]} tensor")
+    if out.numel() == 0:
+        raise ops.PaiError("philox_fill: an empty tensor")
+    ops.philox_fill(code, out, seed, sub, stream, step, param)
+    return out
 
 
 class _PaletteObjective(torch.autograd.Function):

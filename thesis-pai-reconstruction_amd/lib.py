@@ -53,6 +53,8 @@ _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
 _F = C.c_float
+_U32 = C.c_uint32
+_U64 = C.c_uint64
 _D = C.POINTER(ConvDesc)
 
 # name -> (restype, argtypes).  Every symbol declared in include/pai_hip.h is listed here;
@@ -211,6 +213,13 @@ SIGNATURES = {
     "pai_palette_objective_slabs": (_I, [_L]),
     "pai_palette_objective_ws_floats": (_L, [_I, _L]),
     "pai_palette_objective": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _F, _P, _P, _P, _P]),
+    # device random numbers (csrc/philox.h): seed uint64, sub / stream / step / param uint32, by value
+    "pai_philox_fill": (_I, [_I, _P, _L, _U64, _U32, _U32, _U32, _U32, _P]),
+    "pai_film_norm_fwd_rng": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _P, _P, _L, _U64, _U32, _U32, _U32, _F, _I, _P, _P]),
+    "pai_film_norm_bwd_rng": (_I, [_I, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _L, _U64, _U32, _U32, _U32, _F, _I, _P, _P, _P, _P,
+                                   _P, _P]),
+    "pai_palette_noise_rng": (_I, [_P, _P, _P, _I, _I, _L, _I, _U64, _U32, _P, _P, _P, _P, _P]),
+    "pai_palette_step_rng": (_I, [_I, _P, _P, _L, _I, _I, _I, _F, _F, _F, _F, _F, _F, _U64, _U32, _U32, _P, _P, _P]),
 }
 
 _lib = None

@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from ... import functional as PF
 from ... import nnops, ops
-from ...ops import ACT_NONE, ACT_SILU, PaiError
+from ...ops import ACT_NONE, ACT_SILU, STREAM_DROPOUT, PaiError
 
 
 class SiLU(nn.Module):
@@ -172,7 +172,9 @@ class ResBlock(nn.Module):
                 raise PaiError("ResBlock: a resampling block takes one input tensor")
             h, xs = self.h_upd.run_train(h, ctx), self.x_upd.run_train(xs, ctx)
         h = ctx.conv(self.in_layers[2], h, h2)
-        h = ctx.norm(self.out_layers[0], h, emb=ctx.emb[id(self)], p=self.dropout, mask=ctx.masks.get(prefix))
+        mask = ctx.masks.get(prefix)
+        h = ctx.norm(self.out_layers[0], h, emb=ctx.emb[id(self)], p=self.dropout, mask=mask,
+                     rng=None if mask is not None else ctx.rng.get(id(self)))
         h = ctx.conv(self.out_layers[3], h)
         if isinstance(self.skip_connection, nn.Identity):
             s = xs if xs2 is None else torch.cat([xs, xs2], dim=3)       # data movement only
@@ -287,14 +289,15 @@ class _Run:
 
 class _TrainRun:
     """One training pass: the autograd Functions behind the blocks' ``run_train`` methods.  ``emb``: id(ResBlock) -> its
-    [N, 2 C] ``scale | shift`` in the storage dtype; ``masks``: ResBlock prefix -> uint8 NHWC dropout mask."""
+    [N, 2 C] ``scale | shift`` in the storage dtype; ``masks``: ResBlock prefix -> uint8 NHWC dropout mask; ``rng``:
+    id(ResBlock) -> the (seed, stream, step) of its dropout under the device generator (empty: torch draws the masks)."""
 
-    def __init__(self, dtype, emb, masks, capture):
-        self.dtype, self.emb, self.masks, self.capture = dtype, emb, masks, capture
+    def __init__(self, dtype, emb, masks, capture, rng=None):
+        self.dtype, self.emb, self.masks, self.capture, self.rng = dtype, emb, masks, capture, rng or {}
 
     keep = _Run.keep
 
-    def norm(self, bn, x, emb=None, act="silu", p=0.0, mask=None, lo=None, hi=None, count=True, twice=False):
+    def norm(self, bn, x, emb=None, act="silu", p=0.0, mask=None, lo=None, hi=None, count=True, twice=False, rng=None):
         """A norm site on the channels [lo, hi) of ``bn`` (all of them by default); ``count``: this call advances
         ``num_batches_tracked`` (one of the two calls of a norm over a concatenation does)."""
         w, b, mean, var = bn.weight, bn.bias, bn.running_mean, bn.running_var
@@ -302,7 +305,8 @@ class _TrainRun:
             w, b, mean, var = w[lo:hi], b[lo:hi], mean[lo:hi], var[lo:hi]
         return PF.film_norm_act(x, w, b, emb, act=act, dropout_mask=mask, p=float(p), running_mean=mean, running_var=var,
                                 num_batches_tracked=bn.num_batches_tracked if count else None,
-                                momentum=0.1 if bn.momentum is None else bn.momentum, eps=bn.eps, advance_in_backward=twice)
+                                momentum=0.1 if bn.momentum is None else bn.momentum, eps=bn.eps, advance_in_backward=twice,
+                                dropout_rng=rng)
 
     def conv(self, m, x, x2=None):
         w = m.weight
@@ -503,13 +507,16 @@ class UNet(nn.Module):
         parts = nnops.SplitCols.apply(emb_all, tuple(2 * b.out_channel for b in blocks))
         return {id(b): t for b, t in zip(blocks, parts)}
 
-    def forward_train(self, x, y, gammas, dropout_masks=None):
+    def forward_train(self, x, y, gammas, dropout_masks=None, dropout_rng=None):
         """The train-mode pass: x, y fp32 [N x C x H x W] (read as cat([x, y])) and gammas fp32 [N] on the device ->
         fp32 [N x out_channel x H x W], connected by autograd to every parameter (not to the inputs).  Every BatchNorm
         normalises with batch statistics and advances its running buffers as the reference does in one forward + backward:
         once in the forward, the AttentionBlock norms once more in the backward.  ``dropout_masks``: optional dict from a
         ResBlock's prefix below this module (``"input_blocks.1.0"``) to a uint8 NHWC mask of its ``out_layers`` dropout (0
-        drops); a block without an entry draws its own when ``dropout`` > 0.  No host synchronisation."""
+        drops); a block without an entry draws its own when ``dropout`` > 0.  ``dropout_rng = (seed, step)``: the blocks
+        without an entry form their keep bits inside the norm kernels instead (the device generator of csrc/philox.h; the
+        i-th ResBlock in ``modules()`` order has the stream 16 + i), so that no mask tensor exists and torch's generator is
+        not touched.  No host synchronisation."""
         if not self.training:
             raise PaiError("UNet.forward_train is the training pass: call train() first (eval mode samples through forward)")
         if not (x.is_cuda and y.is_cuda and gammas.is_cuda):
@@ -531,7 +538,12 @@ class UNet(nn.Module):
         g = gammas.reshape(-1).float().contiguous()
         if g.shape[0] != x.shape[0]:
             raise PaiError(f"UNet.forward_train: {g.shape[0]} gammas for a batch of {x.shape[0]}")
-        ctx = _TrainRun(dtype, self._embed_train(g, dtype), dict(dropout_masks or {}), self.debug_capture)
+        rng = {}
+        if dropout_rng is not None:
+            seed, step = dropout_rng
+            blocks = [m for m in self.modules() if isinstance(m, ResBlock)]
+            rng = {id(b): (seed, STREAM_DROPOUT + i, step) for i, b in enumerate(blocks)}
+        ctx = _TrainRun(dtype, self._embed_train(g, dtype), dict(dropout_masks or {}), self.debug_capture, rng)
         h, hs = nnops.to_nhwc(torch.cat([x, y], dim=1), dtype), []
         for i, blk in enumerate(self.input_blocks):
             h = blk.run_train(h, None, ctx, f"input_blocks.{i}")

@@ -93,6 +93,37 @@ class DiffusionModel(nn.Module):
         return d[1]
 
 
+class DeviceRNG:
+    """The state of the device generator (csrc/philox.h): a 64-bit ``seed`` and a ``step`` counter, two Python integers.  Every
+    random value of a Palette step is a pure function of (seed, step, site, element index), so a run resumes reproducibly
+    from ``state_dict()``.  ``step`` is the training step or the index of the sampling call: each consumer calls ``advance()``
+    once per call.  Nothing here lives on the device, and nothing is read back from it."""
+
+    def __init__(self, seed: int = 0, step: int = 0):
+        self.seed, self.step = self._check(seed, 64, "seed"), self._check(step, 32, "step")
+
+    @staticmethod
+    def _check(v, bits, what):
+        v = int(v)
+        if not 0 <= v < 1 << bits:
+            raise PaiError(f"DeviceRNG: {what}={v} is not an unsigned {bits}-bit integer")
+        return v
+
+    def advance(self, n: int = 1) -> int:
+        """The step the next call uses; the counter is 32 bits wide and wraps."""
+        self.step = (self.step + int(n)) & 0xFFFFFFFF
+        return self.step
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, state) -> None:
+        self.seed, self.step = self._check(state["seed"], 64, "seed"), self._check(state["step"], 32, "step")
+
+    def __repr__(self):
+        return f"DeviceRNG(seed={self.seed}, step={self.step})"
+
+
 class Palette(LightningModule):
     """Palette image-to-image diffusion model.
 
@@ -113,6 +144,9 @@ class Palette(LightningModule):
         self.save_hyperparameters()
         self.in_channels, self.out_channels, self.learn_var = in_channels, out_channels, learn_var
         self.noise_fn = None        # tests: fn(index, shape) -> fp32 noise; index 0 is y_T, index k the k-th reverse step
+        # a DeviceRNG: every draw of training_loss / forward is formed inside the kernels (csrc/philox.h), torch's generator is
+        # not touched.  None (the default): torch draws, as before.  draws= and noise_fn take precedence where given.
+        self.device_rng = None
         self.unet = UNet(image_size=256, in_channel=in_channels * 2,
                          out_channel=out_channels * 2 if learn_var else out_channels, res_blocks=2, inner_channel=128,
                          channel_mults=tuple(channel_mults), attn_res=tuple(attention_res), num_heads=4, dropout=dropout,
@@ -148,17 +182,26 @@ class Palette(LightningModule):
         def nchw(pixels):
             return pixels.reshape(n, 1, h, w).clone() if c == 1 else pixels.reshape(n, h, w, c).permute(0, 3, 1, 2).contiguous()
 
-        y = self._noise(0, (n, c, h, w), dev)
+        rng = self.device_rng if self.noise_fn is None else None
+        if rng is not None:             # y_T: draw 0 of this sampling call, NHWC pixels as the step kernel numbers them
+            y = PF.philox_fill("normal", (n * h * w, c), rng.seed, 0, ops.STREAM_SAMPLER, rng.step, device=dev)
+        else:
+            y = self._noise(0, (n, c, h, w), dev)
         process = [nchw(y)] if output_process else None
         xy = nnops.to_nhwc(torch.cat([x.to(torch.float32), nchw(y)], dim=1), dt)        # [N, H, W, 2C]: x | y_T
         every = max(steps // 7, 1)
         for k, i in enumerate(reversed(range(steps)), 1):
             eps = self.unet.run(xy, gammas[i], cache)
-            z = self._noise(k, (n, c, h, w), dev)
-            ops.palette_step(dt, eps, y, z, n * h * w, c, self.learn_var, i > 1, table[i], y, xy)
+            if rng is not None:
+                ops.palette_step_rng(dt, eps, y, n * h * w, c, self.learn_var, i > 1, table[i], rng.seed, k, rng.step, y, xy)
+            else:
+                z = self._noise(k, (n, c, h, w), dev)
+                ops.palette_step(dt, eps, y, z, n * h * w, c, self.learn_var, i > 1, table[i], y, xy)
             if output_process and i % every == 0:
                 process.append(nchw(y))
         out = nchw(y)
+        if rng is not None:
+            rng.advance()
         if output_process:
             return out, torch.stack(process, dim=1)
         return out
@@ -176,21 +219,29 @@ class Palette(LightningModule):
         """The loss of one batch ``(x, y_0)`` (fp32 [N x C x H x W] on the device), connected by autograd to the U-Net's
         parameters: t ~ randint(0, timesteps), the forward noising, ``unet.forward_train(x, y_t, gamma)`` and the MSE +
         variational-bound objective.  ``draws = (t, z, u)`` (int [N], fp32 like y_0, fp32 [N]; device tensors) replaces the three
-        draws -- tests, as ``noise_fn`` for the sampler.  Logs ``mse_loss``, ``vlb_loss`` and ``loss``.  No host synchronisation."""
+        draws -- tests, as ``noise_fn`` for the sampler.  With ``device_rng`` set (and no ``draws``) the three draws and every
+        dropout site come from the device generator at (seed, step), and ``step`` advances once per call.  Logs ``mse_loss``,
+        ``vlb_loss`` and ``loss``.  No host synchronisation."""
         x, y_0 = batch
         if not self.training or not self.unet.training:
             raise PaiError("Palette.training_loss runs in train mode: call train() first")
         if not (torch.is_tensor(x) and torch.is_tensor(y_0) and x.is_cuda and y_0.is_cuda):
             raise PaiError("Palette (HIP) needs HIP device tensors; there is no CPU path")
         n, dev = y_0.shape[0], y_0.device
-        if draws is None:
-            t = torch.randint(0, self.diffusion.timesteps, (n,), device=dev)
-            z = torch.randn(y_0.shape, dtype=torch.float32, device=dev)
-            u = torch.rand(n, dtype=torch.float32, device=dev)
+        rng = self.device_rng if draws is None else None
+        if rng is not None:
+            y_t, noise, gamma, t = PF.palette_noise_rng(y_0, rng.seed, rng.step, self.diffusion)
+            model_out = self.unet.forward_train(x, y_t, gamma, dropout_rng=(rng.seed, rng.step))
+            rng.advance()
         else:
-            t, z, u = draws
-        y_t, noise, gamma = PF.palette_noise(y_0, t, u, z, self.diffusion)
-        model_out = self.unet.forward_train(x, y_t, gamma)
+            if draws is None:
+                t = torch.randint(0, self.diffusion.timesteps, (n,), device=dev)
+                z = torch.randn(y_0.shape, dtype=torch.float32, device=dev)
+                u = torch.rand(n, dtype=torch.float32, device=dev)
+            else:
+                t, z, u = draws
+            y_t, noise, gamma = PF.palette_noise(y_0, t, u, z, self.diffusion)
+            model_out = self.unet.forward_train(x, y_t, gamma)
         loss, mse, vlb, _ = PF.palette_objective(model_out, noise, y_0, y_t, t, self.diffusion, self.learn_var)
         self.log("mse_loss", mse, prog_bar=True)
         self.log("vlb_loss", vlb, prog_bar=True)

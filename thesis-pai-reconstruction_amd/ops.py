@@ -1339,3 +1339,79 @@ def palette_objective(model_out, noise, y0, y_t, t, table, N, P, C_, learn_var, 
                                            _p(table, f32), int(table.shape[0]), int(N), int(P), int(C_), int(bool(learn_var)),
                                            float(vlb_weight), _p(out, f32), _p(dout, f32), _p(ws, f32), _stream()),
             "pai_palette_objective")
+
+
+# ---- device random numbers (csrc/philox.h, csrc/philox.hip) -----------------------------------------------------------------
+PHILOX_RAW, PHILOX_UNIFORM, PHILOX_NORMAL, PHILOX_INT, PHILOX_KEEP = 0, 1, 2, 3, 4
+PHILOX_DTYPES = {PHILOX_RAW: torch.int32, PHILOX_UNIFORM: torch.float32, PHILOX_NORMAL: torch.float32, PHILOX_INT: torch.int32,
+                 PHILOX_KEEP: torch.uint8}
+STREAM_T, STREAM_U, STREAM_Z, STREAM_SAMPLER, STREAM_DROPOUT = 0, 1, 2, 3, 16
+
+
+def _u64(v, what="seed") -> int:
+    v = int(v)
+    if not 0 <= v < 1 << 64:
+        raise PaiError(f"{what}={v} is not an unsigned 64-bit integer")
+    return v
+
+
+def _u32(v, what) -> int:
+    v = int(v)
+    if not 0 <= v < 1 << 32:
+        raise PaiError(f"{what}={v} is not an unsigned 32-bit integer")
+    return v
+
+
+def dropout_thr(p: float) -> int:
+    """The 16-bit threshold of a dropout probability: an element is kept iff its 16-bit lane >= round(p * 65536)."""
+    return int(round(float(p) * 65536))
+
+
+def philox_fill(kind, out, seed, sub, stream, step, param=0):
+    """out[0 .. n) = the values of ``kind`` of the Philox tuple (seed, sub, stream, step); out: a contiguous device tensor of
+    ``PHILOX_DTYPES[kind]`` (raw words as the bits of int32), param = T (integer) or thr (keep) (pai_philox_fill)."""
+    L.check(L.load().pai_philox_fill(int(kind), _p(out, PHILOX_DTYPES.get(int(kind), torch.int32)), int(out.numel()), _u64(seed),
+                                     _u32(sub, "sub"), _u32(stream, "stream"), _u32(step, "step"), _u32(param, "param"),
+                                     _stream()), "pai_philox_fill")
+
+
+def film_norm_fwd_rng(dtype, x, rows, N, C_, mean, rstd, gamma, beta, emb, ld, seed, stream, step, thr, keep_scale, act, out):
+    """``film_norm_fwd`` with the keep bits of the Philox tuple (seed, stream, step) and the threshold ``thr`` in place of a mask
+    (pai_film_norm_fwd_rng)."""
+    L.check(L.load().pai_film_norm_fwd_rng(code_of(dtype), _p(x, dtype), int(rows), int(N), int(C_), _p(mean, torch.float32),
+                                           _p(rstd, torch.float32), _p(gamma, torch.float32), _p(beta, torch.float32),
+                                           _p(emb, dtype), int(ld), _u64(seed), _u32(stream, "stream"), _u32(step, "step"),
+                                           _u32(thr, "thr"), float(keep_scale), int(act), _p(out, dtype), _stream()),
+            "pai_film_norm_fwd_rng")
+
+
+def film_norm_bwd_rng(dtype, g, x, rows, N, C_, mean, rstd, gamma, beta, emb, ld, seed, stream, step, thr, keep_scale, act, dx, demb,
+                      dgamma, dbeta, ws):
+    """``film_norm_bwd`` with the keep bits rebuilt from the tuple of the forward (pai_film_norm_bwd_rng)."""
+    L.check(L.load().pai_film_norm_bwd_rng(code_of(dtype), _p(g, dtype), _p(x, dtype), int(rows), int(N), int(C_),
+                                           _p(mean, torch.float32), _p(rstd, torch.float32), _p(gamma, torch.float32),
+                                           _p(beta, torch.float32), _p(emb, dtype), int(ld), _u64(seed), _u32(stream, "stream"),
+                                           _u32(step, "step"), _u32(thr, "thr"), float(keep_scale), int(act), _p(dx, dtype),
+                                           _p(demb, dtype), _p(dgamma, torch.float32), _p(dbeta, torch.float32),
+                                           _p(ws, torch.float32), _stream()), "pai_film_norm_bwd_rng")
+
+
+def palette_noise_rng(y0, gammas, gammas_prev, N, P, C_, seed, step, t, y_t, noise, gamma):
+    """``palette_noise`` with t, u and z drawn inside the launch from (seed, step); ``t`` int32 [N] is written
+    (pai_palette_noise_rng)."""
+    f32 = torch.float32
+    if gammas.numel() != gammas_prev.numel():
+        raise PaiError("palette_noise_rng: gammas and gammas_prev differ in size")
+    L.check(L.load().pai_palette_noise_rng(_p(y0, f32), _p(gammas, f32), _p(gammas_prev, f32), int(gammas.numel()), int(N), int(P),
+                                           int(C_), _u64(seed), _u32(step, "step"), _p(t, torch.int32), _p(y_t, f32),
+                                           _p(noise, f32), _p(gamma, f32), _stream()), "pai_palette_noise_rng")
+
+
+def palette_step_rng(dtype, model_out, y_t, pixels, C_, learn_var, add_noise, scalars, seed, sub, step, y_next, xy_next=None):
+    """``palette_step`` with the noise of draw ``sub`` of the sampling call ``step`` formed inside the launch
+    (pai_palette_step_rng)."""
+    s1, rs, c0, c1, llo, lhi = (float(v) for v in scalars)
+    L.check(L.load().pai_palette_step_rng(code_of(dtype), _p(model_out, dtype), _p(y_t, torch.float32), int(pixels), int(C_),
+                                          int(bool(learn_var)), int(bool(add_noise)), s1, rs, c0, c1, llo, lhi, _u64(seed),
+                                          _u32(sub, "sub"), _u32(step, "step"), _p(y_next, torch.float32), _p(xy_next, dtype),
+                                          _stream()), "pai_palette_step_rng")
