@@ -959,7 +959,8 @@ int pai_palette_objective(const float* model_out, const float* noise, const floa
  * step).  block = flat element index / 4 (/ 8 for keep bits) of the tensor as it lies in memory (NHWC activations, [N][P][C]
  * pixels); sub = 0 except in the sampler, where it is the draw index k (0: y_T, k: the k-th reverse step); stream: 0 = t, 1 = u,
  * 2 = z of the noising, 3 = sampler noise, 16 + i = the dropout of the i-th ResBlock; step = the training step or the index of
- * the sampling call, held on the host and passed by value (no device-to-host copy, no synchronisation).  A tensor that needs
+ * the sampling call, held on the host and passed by value (no device-to-host copy, no synchronisation; the _dev forms at the end
+ * of this header read it from a device counter instead).  A tensor that needs
  * more than 2^32 blocks is refused.  Derived values, w a word of the block:
  *     raw       w itself, four per block
  *     uniform   (w >> 8) 2^-24 in [0, 1), exact; four per block
@@ -1000,6 +1001,38 @@ int pai_palette_noise_rng(const float* y0, const float* gammas, const float* gam
 int pai_palette_step_rng(int dtype, const void* model_out, const float* y_t, int64_t pixels, int C, int learn_var,
                          int add_noise, float s1, float rs, float c0, float c1, float log_lo, float log_hi, uint64_t seed,
                          uint32_t sub, uint32_t step, float* y_next, void* xy_next, void* stream_handle);
+
+/* ---------------------------------------------------------------------------
+ * Device-held step state of the Palette sampler (added under ABI 141, no version change).  A launch plan (pai_plan_*) freezes
+ * every kernel argument by value, so one recorded reverse step can stand for the other steps of the chain, and for the steps
+ * of later sampling calls, only if everything that changes from step to step is read from device memory.  Since this addition
+ * every launch of the Palette entry points above (attention, pai_affine_act, pai_film_coeffs, pai_avgpool2,
+ * pai_gamma_embedding, the reverse step, the noising, the objective, pai_film_norm_*, pai_philox_fill) is recorded by
+ * pai_plan_begin .. pai_plan_end like the launches of the rest of the library.
+ * pai_counter_set / pai_counter_add: *c = v / *c += d on a uint32 in device memory (4-byte aligned), one thread, in stream
+ * order; the sum wraps at 2^32.  Nothing is read back.
+ * pai_philox_fill_dev: pai_philox_fill with the counter word `step` read from *step_dev by every thread (the same kernel body:
+ * for equal values the same bits).  The refusals of pai_philox_fill, and a NULL step_dev.
+ * pai_palette_step_dev: pai_palette_step with the step index on the device.  pos: uint32, k = *pos clamped into [1, T] is the
+ * 1-based index of the reverse step about to be taken, i = T - k its time step.  table: fp32 [T][6], row i = (s1, rs, c0, c1,
+ * log_lo, log_hi) of pai_palette_step (the table of pai_palette_objective); add_noise = i > 1; noise = row k of noise_stack,
+ * fp32 [T + 1][pixels C] (row 0, y_T, is not read).  y_next and the y half of xy_next are written as by pai_palette_step, and
+ * gamma_next[0 .. N) = gammas[max(i - 1, 0)] (gammas: fp32 [T]): the buffer the next U-Net pass's pai_gamma_embedding reads.
+ * The kernel only reads pos: advance it with pai_counter_add(pos, 1) behind this launch, so that no workgroup races another's
+ * read.  Refused before any launch: a NULL tensor, pixels < 1, C < 1, T < 1, N < 1, a size past the int64 / grid limits.
+ * pai_palette_step_rng_dev: the same with noise = the normals of (seed, sub = k, stream 3, step = *rng_step) and no stack.
+ * The arithmetic of all four step entry points is one device function: for equal (i, scalars, noise) the _dev forms give the
+ * bits of pai_palette_step / pai_palette_step_rng. */
+int pai_counter_set(uint32_t* c, uint32_t v, void* stream);
+int pai_counter_add(uint32_t* c, uint32_t d, void* stream);
+int pai_philox_fill_dev(int kind, void* out, int64_t n, uint64_t seed, uint32_t sub, uint32_t stream, const uint32_t* step_dev,
+                        uint32_t param, void* stream_handle);
+int pai_palette_step_dev(int dtype, const void* model_out, const float* y_t, const float* noise_stack, int64_t pixels, int C,
+                         int learn_var, const float* table, int T, const uint32_t* pos, const float* gammas, int N,
+                         float* gamma_next, float* y_next, void* xy_next, void* stream);
+int pai_palette_step_rng_dev(int dtype, const void* model_out, const float* y_t, int64_t pixels, int C, int learn_var,
+                             const float* table, int T, const uint32_t* pos, const float* gammas, int N, float* gamma_next,
+                             uint64_t seed, const uint32_t* rng_step, float* y_next, void* xy_next, void* stream_handle);
 
 #ifdef __cplusplus
 }

@@ -14,12 +14,18 @@ Random normal data throughout (never zeros: MI355X_MICROARCH, data-dependent pow
     python scripts/bench_palette.py [--precision bf16-mixed] [--batch 8] [--size 256] [--steps 100] [--mults 1,1,2,2,4,4]
                                     [--attention-res 16,8] [--no-sampler] [--no-attention] [--forward-only K]
                                     [--no-film-norm] [--film-norm-only] [--train] [--train-only] [--train-batch 4]
-                                    [--count-launches] [--device-rng]
+                                    [--count-launches] [--device-rng] [--planned]
 
 ``--device-rng`` adds a line after every film_norm row (``film_norm_device_rng``: the mask forms, the ``_rng`` forms and the three
 torch launches that draw a mask, timed in turn on the same tensors; ``parent_path_ms`` = draw + forward + backward with a mask
 against ``rng_path_ms`` = the two ``_rng`` calls) and a second sampling call with ``Palette.device_rng`` set
 (``palette_sample_device_rng``).
+``--planned`` runs nothing but the A/B of the planned sampler (``Palette.sampler_plan``) against the eager loop of the same build:
+for every batch size of ``--planned-batches`` (default 1,2,8) one model with ``device_rng`` set, one warm-up call each way, then
+``--planned-rounds`` (default 3) rounds of an eager and a planned sampling call in turn; the medians, the eager rounds' own
+spread (the margin a difference has to clear), the host issue time of one reverse step each way (the Python loop timed
+WITHOUT a synchronisation, on an idle device) beside its GPU time, and ``launches_per_step``.  One ``palette_planned`` line per
+batch size.
 ``--forward-only K`` runs K U-Net forward passes and nothing else (the run to put under a kernel trace); ``--film-norm-only``
 runs the film_norm rows and nothing else (no model is built).
 """
@@ -221,6 +227,46 @@ def bench_train(a, mults, att):
     print(json.dumps(row), flush=True)
 
 
+def bench_planned(a, model, dev):
+    """Eager against planned sampling, interleaved; ``model`` is frozen, at its precision, with a DeviceRNG."""
+    import time
+
+    def call(planned, x):
+        model.sampler_plan = planned
+        t0 = time.perf_counter()
+        a0, b0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a0.record()
+        model(x)
+        b0.record()
+        host = time.perf_counter() - t0             # the loop has been issued; nothing has been waited for
+        torch.cuda.synchronize()
+        return a0.elapsed_time(b0), host * 1e3
+
+    for n in [int(v) for v in a.planned_batches.split(",")]:
+        x = torch.randn(n, 1, a.size, a.size, device=dev)
+        model.device_rng = pai.DeviceRNG(0)
+        for planned in (False, True):               # warm-up: descriptors, workspace, the recording call
+            call(planned, x)
+        seen = {False: [], True: []}
+        for _ in range(max(a.planned_rounds, 3)):
+            for planned in (False, True):
+                seen[planned].append(call(planned, x))
+        med = lambda v: sorted(v)[len(v) // 2]
+        e_ms, p_ms = [g for g, _ in seen[False]], [g for g, _ in seen[True]]
+        e_host, p_host = [h for _, h in seen[False]], [h for _, h in seen[True]]
+        info = model.sampler_plan_info()
+        print(json.dumps({"bench": "palette_planned", "precision": a.precision, "N": n, "size": a.size, "steps": a.steps,
+                          "rounds": len(e_ms), "eager_ms": round(med(e_ms), 2), "planned_ms": round(med(p_ms), 2),
+                          "eager_spread_ms": round(max(e_ms) - min(e_ms), 2), "planned_spread_ms": round(max(p_ms) - min(p_ms), 2),
+                          "eager_all_ms": [round(v, 2) for v in e_ms], "planned_all_ms": [round(v, 2) for v in p_ms],
+                          "eager_step_gpu_ms": round(med(e_ms) / a.steps, 3), "planned_step_gpu_ms": round(med(p_ms) / a.steps, 3),
+                          "eager_step_host_ms": round(med(e_host) / a.steps, 3),
+                          "planned_step_host_ms": round(med(p_host) / a.steps, 3),
+                          "launches_per_step": info["launches_per_step"], "records": info["records"], "replays": info["replays"],
+                          "disabled": info["disabled"]}), flush=True)
+    model.sampler_plan, model.device_rng = False, None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--precision", default="bf16-mixed")
@@ -240,6 +286,9 @@ def main():
     ap.add_argument("--train-only", action="store_true")
     ap.add_argument("--train-batch", type=int, default=4)
     ap.add_argument("--count-launches", action="store_true")
+    ap.add_argument("--planned", action="store_true", help="A/B of the planned sampler against the eager loop, nothing else")
+    ap.add_argument("--planned-batches", default="1,2,8")
+    ap.add_argument("--planned-rounds", type=int, default=3)
     a = ap.parse_args()
     if a.train_only:
         torch.manual_seed(0)
@@ -264,6 +313,9 @@ def main():
     model.freeze()
     model.set_precision(a.precision)
     dtype = model.unet.compute_dtype
+    if a.planned:
+        bench_planned(a, model, dev)
+        return
     x = torch.randn(a.batch, 1, a.size, a.size, device=dev)
     if a.forward_only or not a.no_sampler:
         xy = nnops.to_nhwc(torch.cat([x, torch.randn_like(x)], 1), dtype)

@@ -340,7 +340,7 @@ static int film_norm_fwd_launch(const char* who, int dtype, const void* x, int64
     const dim3 grid(pai_film_norm_slabs(rows), N);
     hipStream_t s = (hipStream_t)stream;
 #define PAI_FN_FWD(TT, ACT)                                                                                                        \
-    hipLaunchKernelGGL((film_norm_fwd_k<TT, ACT, KS>), grid, dim3(256), 0, s, (const TT*)x, rows, G, R, mean, rstd, gamma, beta, \
+    PAI_LAUNCH((film_norm_fwd_k<TT, ACT, KS>), grid, dim3(256), 0, s, (const TT*)x, rows, G, R, mean, rstd, gamma, beta, \
                        (const TT*)emb, ld, keep, keep_scale, (TT*)out)
     if (dtype == PAI_F32) {
         if (act == PAI_ACT_SILU) PAI_FN_FWD(float, PAI_ACT_SILU); else PAI_FN_FWD(float, PAI_ACT_NONE);
@@ -369,11 +369,11 @@ static int film_norm_bwd_launch(const char* who, int dtype, const void* g, const
     const double inv_m = 1.0 / ((double)N * (double)rows);
     hipStream_t s = (hipStream_t)stream;
 #define PAI_FN_BWD(TT, ACT)                                                                                                        \
-    hipLaunchKernelGGL((film_norm_bwd_reduce_k<TT, ACT, KS>), grid, dim3(256), 0, s, (const TT*)g, (const TT*)x, rows, G, R, mean, \
+    PAI_LAUNCH((film_norm_bwd_reduce_k<TT, ACT, KS>), grid, dim3(256), 0, s, (const TT*)g, (const TT*)x, rows, G, R, mean, \
                        rstd, gamma, beta, (const TT*)emb, ld, keep, keep_scale, ws);                                               \
-    hipLaunchKernelGGL((film_norm_bwd_finalize_k<TT>), dim3(C / 8), dim3(1024), 0, s, ws, N, slabs, C, inv_m, gamma, beta,        \
+    PAI_LAUNCH((film_norm_bwd_finalize_k<TT>), dim3(C / 8), dim3(1024), 0, s, ws, N, slabs, C, inv_m, gamma, beta,        \
                        (const TT*)emb, ld, (TT*)demb, dgamma, dbeta);                                                              \
-    hipLaunchKernelGGL((film_norm_bwd_apply_k<TT, ACT, KS>), grid, dim3(256), 0, s, (const TT*)g, (const TT*)x, rows, G, R, mean,  \
+    PAI_LAUNCH((film_norm_bwd_apply_k<TT, ACT, KS>), grid, dim3(256), 0, s, (const TT*)g, (const TT*)x, rows, G, R, mean,  \
                        rstd, gamma, beta, (const TT*)emb, ld, keep, keep_scale, (const float*)tail, (TT*)dx)
     if (dtype == PAI_F32) {
         if (act == PAI_ACT_SILU) { PAI_FN_BWD(float, PAI_ACT_SILU); } else { PAI_FN_BWD(float, PAI_ACT_NONE); }

@@ -688,7 +688,7 @@ static int sattn_forward(const char* who, int dtype, const void* qkv, int N, int
     if (dtype == PAI_BF16) {
         const dim3 grid(cdiv(T, 128), N * heads);
 #define PAI_SATTN_BF16(CH) \
-    hipLaunchKernelGGL((sattn_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, T, heads, scale2, (bf16_t*)out, lse)
+    PAI_LAUNCH((sattn_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, T, heads, scale2, (bf16_t*)out, lse)
         switch (sel.idx) {
             case 0: PAI_SATTN_BF16(32); break;
             case 1: PAI_SATTN_BF16(64); break;
@@ -699,7 +699,7 @@ static int sattn_forward(const char* who, int dtype, const void* qkv, int N, int
     } else {
         const dim3 grid(cdiv(T, 32), N * heads);
 #define PAI_SATTN_F32(CH, KVB) \
-    hipLaunchKernelGGL((sattn_f32_k<CH, KVB>), grid, dim3(256), 0, s, (const float*)qkv, T, heads, scale2, (float*)out, lse)
+    PAI_LAUNCH((sattn_f32_k<CH, KVB>), grid, dim3(256), 0, s, (const float*)qkv, T, heads, scale2, (float*)out, lse)
         switch (sel.idx) {
             case 0: PAI_SATTN_F32(32, 32); break;
             case 1: PAI_SATTN_F32(64, 32); break;
@@ -739,11 +739,11 @@ extern "C" int pai_sattn_bwd(int dtype, const void* dout, const void* qkv, const
     if (dtype == PAI_BF16) {
         const dim3 grid(cdiv(T, 128), N * heads);
 #define PAI_SATTN_BWD_BF16(CH)                                                                                                 \
-    hipLaunchKernelGGL((sattn_bwd_delta_k<bf16_t, CH>), dgrid, dim3(256), 0, s, (const bf16_t*)dout, (const bf16_t*)out, rows, \
+    PAI_LAUNCH((sattn_bwd_delta_k<bf16_t, CH>), dgrid, dim3(256), 0, s, (const bf16_t*)dout, (const bf16_t*)out, rows, \
                        T, heads, ws);                                                                                          \
-    hipLaunchKernelGGL((sattn_bwd_kv_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse,         \
+    PAI_LAUNCH((sattn_bwd_kv_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse,         \
                        (const float*)ws, T, heads, scale2, (bf16_t*)dqkv);                                                     \
-    hipLaunchKernelGGL((sattn_bwd_q_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse,          \
+    PAI_LAUNCH((sattn_bwd_q_bf16_k<CH>), grid, dim3(256), 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse,          \
                        (const float*)ws, T, heads, scale2, (bf16_t*)dqkv)
         switch (sel.idx) {
             case 0: PAI_SATTN_BWD_BF16(32); break;
@@ -754,11 +754,11 @@ extern "C" int pai_sattn_bwd(int dtype, const void* dout, const void* qkv, const
     } else {
         const dim3 grid(cdiv(T, 32), N * heads);
 #define PAI_SATTN_BWD_F32(CH, OB)                                                                                           \
-    hipLaunchKernelGGL((sattn_bwd_delta_k<float, CH>), dgrid, dim3(256), 0, s, (const float*)dout, (const float*)out, rows, \
+    PAI_LAUNCH((sattn_bwd_delta_k<float, CH>), dgrid, dim3(256), 0, s, (const float*)dout, (const float*)out, rows, \
                        T, heads, ws);                                                                                       \
-    hipLaunchKernelGGL((sattn_bwd_f32_k<CH, OB, true>), grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse,  \
+    PAI_LAUNCH((sattn_bwd_f32_k<CH, OB, true>), grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse,  \
                        (const float*)ws, T, heads, scale2, (float*)dqkv);                                                   \
-    hipLaunchKernelGGL((sattn_bwd_f32_k<CH, OB, false>), grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, \
+    PAI_LAUNCH((sattn_bwd_f32_k<CH, OB, false>), grid, dim3(256), 0, s, (const float*)qkv, (const float*)dout, lse, \
                        (const float*)ws, T, heads, scale2, (float*)dqkv)
         switch (sel.idx) {
             case 0: PAI_SATTN_BWD_F32(32, 32); break;
@@ -835,7 +835,7 @@ extern "C" int pai_affine_act(int dtype, const void* x, int64_t rows_per_sample,
     const dim3 grid((unsigned)min((int64_t)4096, (rows_per_sample + (int64_t)R * AV - 1) / ((int64_t)R * AV)), N);
     hipStream_t s = (hipStream_t)stream;
 #define PAI_AFF(TT, ACT) \
-    hipLaunchKernelGGL((affine_act_k<TT, ACT>), grid, dim3(256), 0, s, (const TT*)x, rows_per_sample, G, R, A, B, per_sample, (TT*)out)
+    PAI_LAUNCH((affine_act_k<TT, ACT>), grid, dim3(256), 0, s, (const TT*)x, rows_per_sample, G, R, A, B, per_sample, (TT*)out)
     if (dtype == PAI_F32) {
         if (act == PAI_ACT_SILU) PAI_AFF(float, PAI_ACT_SILU); else PAI_AFF(float, PAI_ACT_NONE);
     } else {
@@ -866,9 +866,9 @@ extern "C" int pai_film_coeffs(int dtype, int C, int N, const float* a, const fl
               (long long)ld);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == PAI_F32)
-        hipLaunchKernelGGL(film_coeffs_k<float>, dim3(cdiv((int64_t)N * C, 256)), dim3(256), 0, s, C, N, a, b, (const float*)emb_out, ld, A, B);
+        PAI_LAUNCH(film_coeffs_k<float>, dim3(cdiv((int64_t)N * C, 256)), dim3(256), 0, s, C, N, a, b, (const float*)emb_out, ld, A, B);
     else
-        hipLaunchKernelGGL(film_coeffs_k<bf16_t>, dim3(cdiv((int64_t)N * C, 256)), dim3(256), 0, s, C, N, a, b, (const bf16_t*)emb_out, ld, A, B);
+        PAI_LAUNCH(film_coeffs_k<bf16_t>, dim3(cdiv((int64_t)N * C, 256)), dim3(256), 0, s, C, N, a, b, (const bf16_t*)emb_out, ld, A, B);
     PAI_LAUNCH_CHECK();
     return 0;
 }
@@ -906,9 +906,9 @@ extern "C" int pai_avgpool2(int dtype, const void* x, int N, int H, int W, int C
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)((nvec + 255) / 256));
     if (dtype == PAI_F32)
-        hipLaunchKernelGGL(avgpool2_k<float>, grid, dim3(256), 0, s, (const float*)x, nvec, H / 2, W / 2, C / 8, (float*)out);
+        PAI_LAUNCH(avgpool2_k<float>, grid, dim3(256), 0, s, (const float*)x, nvec, H / 2, W / 2, C / 8, (float*)out);
     else
-        hipLaunchKernelGGL(avgpool2_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, nvec, H / 2, W / 2, C / 8, (bf16_t*)out);
+        PAI_LAUNCH(avgpool2_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, nvec, H / 2, W / 2, C / 8, (bf16_t*)out);
     PAI_LAUNCH_CHECK();
     return 0;
 }
@@ -949,9 +949,9 @@ extern "C" int pai_avgpool2_bwd(int dtype, const void* dout, int N, int H, int W
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)((nvec + 255) / 256));
     if (dtype == PAI_F32)
-        hipLaunchKernelGGL(avgpool2_bwd_k<float>, grid, dim3(256), 0, s, (const float*)dout, nvec, H / 2, W / 2, C / 8, (float*)dx);
+        PAI_LAUNCH(avgpool2_bwd_k<float>, grid, dim3(256), 0, s, (const float*)dout, nvec, H / 2, W / 2, C / 8, (float*)dx);
     else
-        hipLaunchKernelGGL(avgpool2_bwd_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)dout, nvec, H / 2, W / 2, C / 8, (bf16_t*)dx);
+        PAI_LAUNCH(avgpool2_bwd_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)dout, nvec, H / 2, W / 2, C / 8, (bf16_t*)dx);
     PAI_LAUNCH_CHECK();
     return 0;
 }
@@ -997,9 +997,9 @@ extern "C" int pai_silu_bwd(int dtype, const void* g, const void* u, int64_t num
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)((nthr + 255) / 256));
     if (dtype == PAI_F32)
-        hipLaunchKernelGGL(silu_bwd_k<float>, grid, dim3(256), 0, s, (const float*)g, (const float*)u, numel, (float*)du);
+        PAI_LAUNCH(silu_bwd_k<float>, grid, dim3(256), 0, s, (const float*)g, (const float*)u, numel, (float*)du);
     else
-        hipLaunchKernelGGL(silu_bwd_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)g, (const bf16_t*)u, numel, (bf16_t*)du);
+        PAI_LAUNCH(silu_bwd_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)g, (const bf16_t*)u, numel, (bf16_t*)du);
     PAI_LAUNCH_CHECK();
     return 0;
 }
@@ -1025,9 +1025,9 @@ extern "C" int pai_gamma_embedding(int dtype, const float* gammas, int N, int di
     PAI_CHECK(N >= 1 && dim >= 2 && (int64_t)N * dim < (1ll << 31), "pai_gamma_embedding: N=%d dim=%d", N, dim);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == PAI_F32)
-        hipLaunchKernelGGL(gamma_embedding_k<float>, dim3(cdiv((int64_t)N * dim, 256)), dim3(256), 0, s, gammas, N, dim, (float*)out);
+        PAI_LAUNCH(gamma_embedding_k<float>, dim3(cdiv((int64_t)N * dim, 256)), dim3(256), 0, s, gammas, N, dim, (float*)out);
     else
-        hipLaunchKernelGGL(gamma_embedding_k<bf16_t>, dim3(cdiv((int64_t)N * dim, 256)), dim3(256), 0, s, gammas, N, dim, (bf16_t*)out);
+        PAI_LAUNCH(gamma_embedding_k<bf16_t>, dim3(cdiv((int64_t)N * dim, 256)), dim3(256), 0, s, gammas, N, dim, (bf16_t*)out);
     PAI_LAUNCH_CHECK();
     return 0;
 }
@@ -1037,10 +1037,12 @@ extern "C" int pai_gamma_embedding(int dtype, const float* gammas, int N, int di
 // (learn_var) or log_lo; y_{t-1} = mean + exp(0.5 log variance) noise (add_noise) -- the expression order of
 // palette.py:233-306.  Pixels are [pixel][channel]; the model output has C (or, learn_var, 2 C: eps | var) columns.
 // RNG: the noise of element i is normal i of the Philox tuple `key` (stream 3, sub = the draw index), not noise[i].
+// One body for the four kernels below: the by-value forms and the device-state forms differ only in where (i, the six scalars,
+// the noise) come from, so for equal values they give equal bits.
 template <typename T, bool RNG>
-__global__ __launch_bounds__(256) void palette_step_k(const T* mo, const float* y_t, const float* noise, PhiloxKey key, int64_t numel,
-                                                      int C, int learn_var, int add_noise, float s1, float rs, float c0, float c1,
-                                                      float log_lo, float log_hi, float* y_next, T* xy_next) {
+__device__ __forceinline__ void palette_step_body(const T* mo, const float* y_t, const float* noise, const PhiloxKey& key,
+                                                  int64_t numel, int C, int learn_var, int add_noise, float s1, float rs, float c0,
+                                                  float c1, float log_lo, float log_hi, float* y_next, T* xy_next) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= numel) return;
     const int64_t px = i / C;
@@ -1063,6 +1065,42 @@ __global__ __launch_bounds__(256) void palette_step_k(const T* mo, const float* 
     if (xy_next) Conv<T>::st(xy_next + px * 2 * C + C + c, out);
 }
 
+template <typename T, bool RNG>
+__global__ __launch_bounds__(256) void palette_step_k(const T* mo, const float* y_t, const float* noise, PhiloxKey key, int64_t numel,
+                                                      int C, int learn_var, int add_noise, float s1, float rs, float c0, float c1,
+                                                      float log_lo, float log_hi, float* y_next, T* xy_next) {
+    palette_step_body<T, RNG>(mo, y_t, noise, key, numel, C, learn_var, add_noise, s1, rs, c0, c1, log_lo, log_hi, y_next, xy_next);
+}
+
+// The step whose index lives on the device (a recorded launch stands for every step of the chain): k = *pos clamped into [1, T]
+// is the 1-based index of the reverse step, i = T - k its row of `table` (fp32 [T][6], the scalars of palette_step_k in its
+// argument order), add_noise = i > 1, the noise row k of noise_stack [T + 1][numel] or (RNG) Philox at sub = k, step = *rng_step.
+// The first workgroup also writes gamma_next[0 .. N) = gammas[max(i - 1, 0)], the noise level the NEXT U-Net pass embeds.
+// pos and rng_step are only read: every workgroup reads them, and the launch that advances pos comes behind this one.
+template <typename T, bool RNG>
+__global__ __launch_bounds__(256) void palette_step_dev_k(const T* mo, const float* y_t, const float* noise_stack, PhiloxKey key,
+                                                          const uint32_t* rng_step, int64_t numel, int C, int learn_var,
+                                                          const float* table, int Tn, const uint32_t* pos, const float* gammas,
+                                                          int N, float* gamma_next, float* y_next, T* xy_next) {
+    uint32_t k = *pos;
+    k = k < 1u ? 1u : (k > (uint32_t)Tn ? (uint32_t)Tn : k);
+    const int i = Tn - (int)k;
+    if (blockIdx.x == 0) {
+        const float g = gammas[i > 0 ? i - 1 : 0];
+        for (int n = threadIdx.x; n < N; n += 256) gamma_next[n] = g;
+    }
+    const float* row = table + 6 * i;
+    const float* noise = nullptr;
+    if (RNG) {
+        key.sub = k;
+        key.step = *rng_step;
+    } else {
+        noise = noise_stack + (int64_t)k * numel;
+    }
+    palette_step_body<T, RNG>(mo, y_t, noise, key, numel, C, learn_var, i > 1 ? 1 : 0, row[0], row[1], row[2], row[3], row[4], row[5],
+                              y_next, xy_next);
+}
+
 template <bool RNG>
 static int palette_step_launch(const char* who, int dtype, const void* model_out, const float* y_t, const float* noise, PhiloxKey key,
                                int64_t pixels, int C, int learn_var, int add_noise, float s1, float rs, float c0, float c1,
@@ -1076,10 +1114,10 @@ static int palette_step_launch(const char* who, int dtype, const void* model_out
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)((numel + 255) / 256));
     if (dtype == PAI_F32)
-        hipLaunchKernelGGL((palette_step_k<float, RNG>), grid, dim3(256), 0, s, (const float*)model_out, y_t, noise, key, numel, C,
+        PAI_LAUNCH((palette_step_k<float, RNG>), grid, dim3(256), 0, s, (const float*)model_out, y_t, noise, key, numel, C,
                            learn_var, add_noise, s1, rs, c0, c1, log_lo, log_hi, y_next, (float*)xy_next);
     else
-        hipLaunchKernelGGL((palette_step_k<bf16_t, RNG>), grid, dim3(256), 0, s, (const bf16_t*)model_out, y_t, noise, key, numel, C,
+        PAI_LAUNCH((palette_step_k<bf16_t, RNG>), grid, dim3(256), 0, s, (const bf16_t*)model_out, y_t, noise, key, numel, C,
                            learn_var, add_noise, s1, rs, c0, c1, log_lo, log_hi, y_next, (bf16_t*)xy_next);
     PAI_LAUNCH_CHECK();
     return 0;
@@ -1098,6 +1136,48 @@ extern "C" int pai_palette_step_rng(int dtype, const void* model_out, const floa
     return palette_step_launch<true>("pai_palette_step_rng", dtype, model_out, y_t, nullptr,
                                      philox_key(seed, sub, PHILOX_STREAM_SAMPLER, step), pixels, C, learn_var, add_noise, s1, rs, c0,
                                      c1, log_lo, log_hi, y_next, xy_next, stream_handle);
+}
+
+template <bool RNG>
+static int palette_step_dev_launch(const char* who, int dtype, const void* model_out, const float* y_t, const float* noise_stack,
+                                   PhiloxKey key, const uint32_t* rng_step, int64_t pixels, int C, int learn_var, const float* table,
+                                   int T, const uint32_t* pos, const float* gammas, int N, float* gamma_next, float* y_next,
+                                   void* xy_next, void* stream) {
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "%s: dtype=%d", who, dtype);
+    PAI_CHECK(model_out && y_t && y_next && table && pos && gammas && gamma_next && (RNG ? rng_step != nullptr : noise_stack != nullptr),
+              "%s: null tensor", who);
+    PAI_CHECK(pixels >= 1 && C >= 1, "%s: pixels=%lld C=%d", who, (long long)pixels, C);
+    PAI_CHECK(T >= 1 && N >= 1, "%s: T=%d N=%d", who, T, N);
+    PAI_CHECK(!RNG || pixels <= (1ll << 34) / C, "%s: tensor too large (more than 2^32 blocks of 4)", who);
+    PAI_CHECK(pixels <= (1ll << 62) / C / ((int64_t)T + 1), "%s: tensor too large", who);
+    const int64_t numel = pixels * C;
+    PAI_CHECK((numel + 255) / 256 < (1ll << 31), "%s: tensor too large", who);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((numel + 255) / 256));
+    if (dtype == PAI_F32)
+        PAI_LAUNCH((palette_step_dev_k<float, RNG>), grid, dim3(256), 0, s, (const float*)model_out, y_t, noise_stack, key, rng_step,
+                   numel, C, learn_var, table, T, pos, gammas, N, gamma_next, y_next, (float*)xy_next);
+    else
+        PAI_LAUNCH((palette_step_dev_k<bf16_t, RNG>), grid, dim3(256), 0, s, (const bf16_t*)model_out, y_t, noise_stack, key, rng_step,
+                   numel, C, learn_var, table, T, pos, gammas, N, gamma_next, y_next, (bf16_t*)xy_next);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pai_palette_step_dev(int dtype, const void* model_out, const float* y_t, const float* noise_stack, int64_t pixels,
+                                    int C, int learn_var, const float* table, int T, const uint32_t* pos, const float* gammas, int N,
+                                    float* gamma_next, float* y_next, void* xy_next, void* stream) {
+    return palette_step_dev_launch<false>("pai_palette_step_dev", dtype, model_out, y_t, noise_stack, PhiloxKey{}, nullptr, pixels, C,
+                                          learn_var, table, T, pos, gammas, N, gamma_next, y_next, xy_next, stream);
+}
+
+extern "C" int pai_palette_step_rng_dev(int dtype, const void* model_out, const float* y_t, int64_t pixels, int C, int learn_var,
+                                        const float* table, int T, const uint32_t* pos, const float* gammas, int N,
+                                        float* gamma_next, uint64_t seed, const uint32_t* rng_step, float* y_next, void* xy_next,
+                                        void* stream_handle) {
+    return palette_step_dev_launch<true>("pai_palette_step_rng_dev", dtype, model_out, y_t, nullptr,
+                                         philox_key(seed, 0, PHILOX_STREAM_SAMPLER, 0), rng_step, pixels, C, learn_var, table, T, pos,
+                                         gammas, N, gamma_next, y_next, xy_next, stream_handle);
 }
 
 // ---- forward noising q(y_t | y_0) ----------------------------------------------------------------------------------------------------
@@ -1182,10 +1262,10 @@ static int palette_noise_launch(const char* who, const float* y0, const float* z
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)chunks, (unsigned)N);
     if (vec)
-        hipLaunchKernelGGL((palette_noise_k<true, RNG>), grid, dim3(256), 0, s, y0, z, u, t, key, t_out, gammas, gammas_prev, T, PC,
+        PAI_LAUNCH((palette_noise_k<true, RNG>), grid, dim3(256), 0, s, y0, z, u, t, key, t_out, gammas, gammas_prev, T, PC,
                            y_t, noise, gamma);
     else
-        hipLaunchKernelGGL((palette_noise_k<false, RNG>), grid, dim3(256), 0, s, y0, z, u, t, key, t_out, gammas, gammas_prev, T, PC,
+        PAI_LAUNCH((palette_noise_k<false, RNG>), grid, dim3(256), 0, s, y0, z, u, t, key, t_out, gammas, gammas_prev, T, PC,
                            y_t, noise, gamma);
     PAI_LAUNCH_CHECK();
     return 0;
@@ -1423,10 +1503,10 @@ extern "C" int pai_palette_objective(const float* model_out, const float* noise,
 #define PAI_POBJ_VEC(CC)                                                                                                          \
     case CC:                                                                                                                      \
         if (learn_var)                                                                                                            \
-            hipLaunchKernelGGL((palette_objective_vec_k<CC, true>), grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, \
+            PAI_LAUNCH((palette_objective_vec_k<CC, true>), grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, \
                                pps, ge, gvs, dout, w);                                                                            \
         else                                                                                                                      \
-            hipLaunchKernelGGL((palette_objective_vec_k<CC, false>), grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, \
+            PAI_LAUNCH((palette_objective_vec_k<CC, false>), grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, \
                                pps, ge, gvs, dout, w);                                                                            \
         break;
     if (P % 4 == 0) {
@@ -1437,15 +1517,15 @@ extern "C" int pai_palette_objective(const float* model_out, const float* noise,
             PAI_POBJ_VEC(4)
         }
     } else if (learn_var) {
-        hipLaunchKernelGGL(palette_objective_px_k<true>, grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, pps, C, ge,
+        PAI_LAUNCH(palette_objective_px_k<true>, grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, pps, C, ge,
                            gvs, dout, w);
     } else {
-        hipLaunchKernelGGL(palette_objective_px_k<false>, grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, pps, C, ge,
+        PAI_LAUNCH(palette_objective_px_k<false>, grid, dim3(256), 0, s, model_out, noise, y0, y_t, t, table, T, P, pps, C, ge,
                            gvs, dout, w);
     }
 #undef PAI_POBJ_VEC
     PAI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(palette_objective_fin_k, dim3(1), dim3(256), 0, s, (const double*)w, N, slabs, 1.0 / npc,
+    PAI_LAUNCH(palette_objective_fin_k, dim3(1), dim3(256), 0, s, (const double*)w, N, slabs, 1.0 / npc,
                        1.0 / ((double)P * (double)C * 0.6931471805599453), vlb_weight, out);
     PAI_LAUNCH_CHECK();
     return 0;

@@ -8,7 +8,8 @@
 //   block   = flat element index / 4 (uniform, normal, integer, raw) or / 8 (keep bits) of the tensor as it lies in memory
 //   sub     = 0, except in the sampler: the draw index k (0 is y_T, k the k-th reverse step)
 //   stream  = PHILOX_STREAM_T | _U | _Z | _SAMPLER, or PHILOX_STREAM_DROPOUT + i for the i-th ResBlock
-//   step    = the training step or the index of the sampling call, passed by value
+//   step    = the training step or the index of the sampling call, passed by value -- or, in the _dev forms the planned sampler
+//             records, read from a uint32 in device memory (the mirror of DeviceRNG.step)
 // Derived values (fixed: the tests are bit-exact against a host restatement):
 //   uniform   (w >> 8) 2^-24 in [0, 1), exact; four per block
 //   integer   __umulhi(w, T) in [0, T); four per block

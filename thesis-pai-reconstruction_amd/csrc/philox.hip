@@ -5,7 +5,7 @@
 #include "philox.h"
 
 template <int KIND>
-__global__ __launch_bounds__(256) void philox_fill_k(void* out, int64_t n, PhiloxKey key, uint32_t param, int vec) {
+__device__ __forceinline__ void philox_fill_body(void* out, int64_t n, const PhiloxKey& key, uint32_t param, int vec) {
     constexpr int E = KIND == PAI_PHILOX_KEEP ? 8 : 4;
     const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t i0 = b * E;
@@ -45,22 +45,62 @@ __global__ __launch_bounds__(256) void philox_fill_k(void* out, int64_t n, Philo
     }
 }
 
-extern "C" int pai_philox_fill(int kind, void* out, int64_t n, uint64_t seed, uint32_t sub, uint32_t stream, uint32_t step,
-                               uint32_t param, void* stream_handle) {
-    PAI_CHECK(kind >= PAI_PHILOX_RAW && kind <= PAI_PHILOX_KEEP, "pai_philox_fill: kind=%d", kind);
-    PAI_CHECK(out, "pai_philox_fill: null tensor");
-    PAI_CHECK(n >= 1, "pai_philox_fill: n=%lld", (long long)n);
-    PAI_CHECK(kind != PAI_PHILOX_INT || (param >= 1 && param <= 0x7fffffffu), "pai_philox_fill: T=%u (1 .. 2^31 - 1)", param);
-    PAI_CHECK(kind != PAI_PHILOX_KEEP || param <= 65536u, "pai_philox_fill: thr=%u (round(p 65536), at most 65536)", param);
+template <int KIND>
+__global__ __launch_bounds__(256) void philox_fill_k(void* out, int64_t n, PhiloxKey key, uint32_t param, int vec) {
+    philox_fill_body<KIND>(out, n, key, param, vec);
+}
+
+// the same body with counter word 3 read from device memory: a recorded launch follows a step counter that advances on the device
+template <int KIND>
+__global__ __launch_bounds__(256) void philox_fill_dev_k(void* out, int64_t n, PhiloxKey key, const uint32_t* step_dev, uint32_t param,
+                                                         int vec) {
+    key.step = *step_dev;
+    philox_fill_body<KIND>(out, n, key, param, vec);
+}
+
+// ---- device-held counters: the sampler's step index and the mirror of DeviceRNG.step ---------------------------------------------
+// One thread, plain loads and stores; unsigned arithmetic wraps at 2^32 as DeviceRNG.advance does on the host.
+__global__ void counter_set_k(uint32_t* c, uint32_t v) { *c = v; }
+__global__ void counter_add_k(uint32_t* c, uint32_t d) { *c = *c + d; }
+
+extern "C" int pai_counter_set(uint32_t* c, uint32_t v, void* stream) {
+    PAI_CHECK(c, "pai_counter_set: null counter");
+    PAI_CHECK((uintptr_t)c % 4 == 0, "pai_counter_set: the counter is not aligned to 4 bytes");
+    PAI_LAUNCH(counter_set_k, dim3(1), dim3(1), 0, (hipStream_t)stream, c, v);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pai_counter_add(uint32_t* c, uint32_t d, void* stream) {
+    PAI_CHECK(c, "pai_counter_add: null counter");
+    PAI_CHECK((uintptr_t)c % 4 == 0, "pai_counter_add: the counter is not aligned to 4 bytes");
+    PAI_LAUNCH(counter_add_k, dim3(1), dim3(1), 0, (hipStream_t)stream, c, d);
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+// the refusals and the launch geometry shared by pai_philox_fill and pai_philox_fill_dev
+static int philox_fill_launch(const char* who, int kind, void* out, int64_t n, uint64_t seed, uint32_t sub, uint32_t stream,
+                              uint32_t step, const uint32_t* step_dev, bool dev, uint32_t param, void* stream_handle) {
+    PAI_CHECK(kind >= PAI_PHILOX_RAW && kind <= PAI_PHILOX_KEEP, "%s: kind=%d", who, kind);
+    PAI_CHECK(out, "%s: null tensor", who);
+    PAI_CHECK(!dev || step_dev, "%s: null step counter", who);
+    PAI_CHECK(n >= 1, "%s: n=%lld", who, (long long)n);
+    PAI_CHECK(kind != PAI_PHILOX_INT || (param >= 1 && param <= 0x7fffffffu), "%s: T=%u (1 .. 2^31 - 1)", who, param);
+    PAI_CHECK(kind != PAI_PHILOX_KEEP || param <= 65536u, "%s: thr=%u (round(p 65536), at most 65536)", who, param);
     const int E = kind == PAI_PHILOX_KEEP ? 8 : 4, esz = kind == PAI_PHILOX_KEEP ? 1 : 4;
-    PAI_CHECK((uintptr_t)out % esz == 0, "pai_philox_fill: out is not aligned to its element type");
+    PAI_CHECK((uintptr_t)out % esz == 0, "%s: out is not aligned to its element type", who);
     const int64_t blocks = (n - 1) / E + 1;
-    PAI_CHECK(blocks <= (1ll << 32), "pai_philox_fill: tensor too large (more than 2^32 blocks of %d)", E);
+    PAI_CHECK(blocks <= (1ll << 32), "%s: tensor too large (more than 2^32 blocks of %d)", who, E);
     const int vec = (uintptr_t)out % (E * esz) == 0;
     const dim3 grid((unsigned)((blocks + 255) / 256));
     const PhiloxKey key = philox_key(seed, sub, stream, step);
     hipStream_t s = (hipStream_t)stream_handle;
-#define PAI_PHILOX_FILL(K) hipLaunchKernelGGL(philox_fill_k<K>, grid, dim3(256), 0, s, out, n, key, param, vec)
+#define PAI_PHILOX_FILL(K)                                                                              \
+    do {                                                                                                \
+        if (dev) PAI_LAUNCH(philox_fill_dev_k<K>, grid, dim3(256), 0, s, out, n, key, step_dev, param, vec); \
+        else PAI_LAUNCH(philox_fill_k<K>, grid, dim3(256), 0, s, out, n, key, param, vec);              \
+    } while (0)
     switch (kind) {
         case PAI_PHILOX_RAW: PAI_PHILOX_FILL(PAI_PHILOX_RAW); break;
         case PAI_PHILOX_UNIFORM: PAI_PHILOX_FILL(PAI_PHILOX_UNIFORM); break;
@@ -71,4 +111,14 @@ extern "C" int pai_philox_fill(int kind, void* out, int64_t n, uint64_t seed, ui
 #undef PAI_PHILOX_FILL
     PAI_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int pai_philox_fill(int kind, void* out, int64_t n, uint64_t seed, uint32_t sub, uint32_t stream, uint32_t step,
+                               uint32_t param, void* stream_handle) {
+    return philox_fill_launch("pai_philox_fill", kind, out, n, seed, sub, stream, step, nullptr, false, param, stream_handle);
+}
+
+extern "C" int pai_philox_fill_dev(int kind, void* out, int64_t n, uint64_t seed, uint32_t sub, uint32_t stream,
+                                   const uint32_t* step_dev, uint32_t param, void* stream_handle) {
+    return philox_fill_launch("pai_philox_fill_dev", kind, out, n, seed, sub, stream, 0, step_dev, true, param, stream_handle);
 }

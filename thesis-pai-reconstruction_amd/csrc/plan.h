@@ -1,4 +1,6 @@
-// Launch plans: every kernel launch of libpai_hip.so goes through pai::launch.  While a plan is being recorded
+// Launch plans: every kernel launch of libpai_hip.so goes through pai::launch (PAI_LAUNCH) -- since the Palette sampler plans
+// its reverse step that holds for palette.hip, film_norm.hip and philox.hip too, which used to launch directly and were
+// silently missing from a plan recorded around them.  While a plan is being recorded
 // (pai_plan_begin ... pai_plan_end) each launch is executed AND appended to the plan with its kernel handle, grid, block,
 // LDS size, stream and a by-value copy of its arguments; pai_plan_run then re-issues the whole sequence -- the ~205
 // launches of a Pix2Pix GAN step on their three streams, with the cross-stream event edges recorded through

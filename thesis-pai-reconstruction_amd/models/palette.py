@@ -12,6 +12,9 @@ The sample chain stays fp32 in both precisions, as NHWC pixels; the U-Net reads 
 one tensor whose y half the step kernel rewrites.  The six scalars of each step come from a table built once on the
 host from the fp32 schedule buffers in the reference's expression order; the loop copies nothing back to the host.
 
+``sampler_plan`` (opt-in; PAI_PALETTE_PLAN=1) replays the reverse step from a recorded launch plan instead of issuing its ~400
+launches from Python at every step: see "the planned sampler" below and DESIGN.md 7c.
+
 Reference behaviour kept on purpose: the sampler adds noise while ``t > 1`` (palette.py:250), not ``t > 0``.
 """
 import os
@@ -97,10 +100,19 @@ class DeviceRNG:
     """The state of the device generator (csrc/philox.h): a 64-bit ``seed`` and a ``step`` counter, two Python integers.  Every
     random value of a Palette step is a pure function of (seed, step, site, element index), so a run resumes reproducibly
     from ``state_dict()``.  ``step`` is the training step or the index of the sampling call: each consumer calls ``advance()``
-    once per call.  Nothing here lives on the device, and nothing is read back from it."""
+    once per call.  The two integers are the truth (``state_dict`` / ``load_state_dict`` / ``--resume``), and nothing is ever
+    read back from the device.
+
+    A consumer whose launches are replayed from a recorded plan (the planned sampler) cannot take ``step`` by value: it asks
+    ``device_step(device)`` for a uint32 device scalar that mirrors it.  The mirror of a device is created on that first
+    request; from then on ``advance()`` moves it with ``pai_counter_add`` in stream order, and the next request rewrites it
+    with ``pai_counter_set`` whenever the host value is not the one the mirror was last given (first use,
+    ``load_state_dict``, an assignment to ``step``).  Without such a consumer no mirror exists and nothing is launched.  A
+    mirror follows the host in the order of ONE stream: consumers on different streams need generators of their own."""
 
     def __init__(self, seed: int = 0, step: int = 0):
         self.seed, self.step = self._check(seed, 64, "seed"), self._check(step, 32, "step")
+        self._mirrors = {}          # device index -> [int32 device scalar (the bits of the uint32), the value it holds]
 
     @staticmethod
     def _check(v, bits, what):
@@ -111,8 +123,30 @@ class DeviceRNG:
 
     def advance(self, n: int = 1) -> int:
         """The step the next call uses; the counter is 32 bits wide and wraps."""
-        self.step = (self.step + int(n)) & 0xFFFFFFFF
+        old = self.step
+        self.step = (old + int(n)) & 0xFFFFFFFF
+        for m in self._mirrors.values():
+            if m[1] == old:                     # in step with the host: stays so; otherwise the next request rewrites it
+                with torch.cuda.device(m[0].device):
+                    ops.counter_add(m[0], int(n) & 0xFFFFFFFF)
+                m[1] = self.step
         return self.step
+
+    def device_step(self, device) -> torch.Tensor:
+        """The device scalar (int32 storage, uint32 bits) that holds ``step`` in the order of the current stream of ``device``."""
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise PaiError("DeviceRNG.device_step needs a HIP device")
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        m = self._mirrors.get(idx)
+        if m is None:
+            m = self._mirrors[idx] = [torch.empty(1, dtype=torch.int32, device=torch.device("cuda", idx)), None]
+        step = self._check(self.step, 32, "step")
+        if m[1] != step:
+            with torch.cuda.device(m[0].device):
+                ops.counter_set(m[0], step)
+            m[1] = step
+        return m[0]
 
     def state_dict(self) -> dict:
         return {"seed": self.seed, "step": self.step}
@@ -122,6 +156,40 @@ class DeviceRNG:
 
     def __repr__(self):
         return f"DeviceRNG(seed={self.seed}, step={self.step})"
+
+
+def sampler_plan_default() -> bool:
+    """PAI_PALETTE_PLAN=1 makes the planned sampler the default of every Palette constructed afterwards (A/B of report.py
+    and of validation without a command-line change)."""
+    return os.environ.get("PAI_PALETTE_PLAN", "0") not in ("", "0")
+
+
+class _StepPlan:
+    """What one recorded reverse step owns: the static buffers its launches read and write, the plan, and everything the plan's
+    frozen pointers need alive (the pass's activations, the weight cache)."""
+    __slots__ = ("sig", "cache", "xy", "y", "gamma_next", "pos", "noise_stack", "warmed", "plan", "keep", "consts")
+
+
+class _SamplerPlans:
+    """The plans of one Palette, most recently used last, and the counters of ``sampler_plan_info``."""
+    MAX_PLANS = 4           # each one pins one U-Net pass of activations
+
+    def __init__(self):
+        from collections import OrderedDict
+        self.plans = OrderedDict()
+        self.records = self.replays = 0
+        self.disabled = None            # why calls run eagerly; ``sticky``: for good (a kernel the recorder cannot own)
+        self.sticky = False
+        self.launches_per_step = None
+
+    def __deepcopy__(self, memo):       # a copied model records its own plans
+        return _SamplerPlans()
+
+    def __getstate__(self):
+        return {}
+
+    def __setstate__(self, state):
+        self.__init__()
 
 
 class Palette(LightningModule):
@@ -147,6 +215,9 @@ class Palette(LightningModule):
         # a DeviceRNG: every draw of training_loss / forward is formed inside the kernels (csrc/philox.h), torch's generator is
         # not touched.  None (the default): torch draws, as before.  draws= and noise_fn take precedence where given.
         self.device_rng = None
+        # the planned sampler (``_forward_planned``): opt-in; PAI_PALETTE_PLAN=1 sets the default of new objects
+        self.sampler_plan = sampler_plan_default()
+        self._splan = _SamplerPlans()
         self.unet = UNet(image_size=256, in_channel=in_channels * 2,
                          out_channel=out_channels * 2 if learn_var else out_channels, res_blocks=2, inner_channel=128,
                          channel_mults=tuple(channel_mults), attn_res=tuple(attention_res), num_heads=4, dropout=dropout,
@@ -176,6 +247,10 @@ class Palette(LightningModule):
         steps, table = inf.timesteps, inf.step_table()
         if self.unet.training:
             raise PaiError("Palette.forward samples in eval mode: call eval() / freeze() first")
+        if self.sampler_plan:
+            mode = self._plan_mode()
+            if mode is not None:
+                return self._forward_planned(x, output_process, mode)
         cache = self.unet.prepared(dt)
         gammas = inf.gammas.to(dev).reshape(steps, 1).expand(steps, n).contiguous()      # row i: the U-Net's gammas of step i
 
@@ -205,6 +280,152 @@ class Palette(LightningModule):
         if output_process:
             return out, torch.stack(process, dim=1)
         return out
+
+    # ---- the planned sampler ---------------------------------------------------------------------------------------------
+    # One reverse step -- the U-Net pass, the step kernel, the advance of the step index: ~400 launches -- is recorded once
+    # into a launch plan (ops.Plan, csrc/plan.h) and replayed from one C call for the other steps of the chain and for every
+    # step of later calls.  What changes from step to step is on the device: the U-Net reads a fixed ``xy`` and a fixed
+    # ``gamma_next``; the step kernel (pai_palette_step_dev / _rng_dev) takes its scalars, its noise and the next pass's
+    # gamma from the step index ``pos``, and the generator's step from DeviceRNG's device mirror.  Per call, outside the plan:
+    # x | y_T into ``xy``, the first gamma, pos = 1, and the final layout change.  Same kernels, same arithmetic, same stream
+    # as the eager loop: the same bits.
+    def _plan_mode(self):
+        """"noise" | "rng" when this call can run from a plan, None (with the reason in ``sampler_plan_info()``) otherwise."""
+        st = self._splan
+        if st.sticky:
+            return None
+        if ops.PROFILE is not None or ops.PROFILE_HBM is not None:
+            st.disabled = "per-launch event profiling is on"
+        elif self.unet.debug_capture is not None:
+            st.disabled = "the U-Net's debug capture is on (torch kernels inside the pass)"
+        elif self.noise_fn is not None:
+            st.disabled = None
+            return "noise"
+        elif self.device_rng is not None:
+            st.disabled = None
+            return "rng"
+        else:
+            st.disabled = ("torch draws the noise (neither device_rng nor noise_fn is set): torch.randn per step is a kernel "
+                           "the plan cannot own")
+        return None
+
+    def _plan_sig(self, shape, dt, dev, mode, cache, table, gammas):
+        h = ops.handle_for(dev)
+        rng = self.device_rng if mode == "rng" else None
+        return (tuple(shape), dt, dev.index, ops._stream(), bool(self.learn_var), int(table.shape[0]), mode, id(cache),
+                tuple(t.data_ptr() if t is not None else 0 for t in (h.workspace, h.scratch)), table.data_ptr(),
+                gammas.data_ptr(), None if rng is None else (rng.seed, rng.device_step(dev).data_ptr()))
+
+    def _plan_step(self, rec, dt, n, npx, c, table, gammas, mode, dev):
+        """One reverse step on the static buffers of ``rec``: what is recorded, and what runs un-recorded before that."""
+        eps = self.unet.run(rec.xy, rec.gamma_next, rec.cache)
+        if mode == "rng":
+            rng = self.device_rng
+            ops.palette_step_rng_dev(dt, eps, rec.y, npx, c, self.learn_var, table, rec.pos, gammas, n, rec.gamma_next, rng.seed,
+                                     rng.device_step(dev), rec.y, rec.xy)
+        else:
+            ops.palette_step_dev(dt, eps, rec.y, rec.noise_stack, npx, c, self.learn_var, table, rec.pos, gammas, n, rec.gamma_next,
+                                 rec.y, rec.xy)
+        ops.counter_add(rec.pos, 1)
+
+    def _plan_record(self, rec, *step_args):
+        """Run one step while it is recorded.  False: the recorder saw a kernel of torch's own, the sampler stays eager."""
+        from ..plan import _Recorder
+        st = self._splan
+        recorder = _Recorder()
+        with recorder:
+            recorder.begin()
+            try:
+                self._plan_step(rec, *step_args)
+            finally:
+                recorder.end()
+        st.records += 1
+        if recorder.foreign or len(recorder.items) != 1:
+            kinds = sorted(set(recorder.foreign))
+            st.disabled = ("the reverse step launches kernels outside the C ABI (" + ", ".join(kinds[:8]) +
+                           (", ..." if len(kinds) > 8 else "") + "): it cannot be replayed from a plan") if kinds else \
+                "the recorded step is not one plan segment"
+            st.sticky = True
+            st.plans.clear()
+            return False
+        rec.plan, rec.keep = recorder.items[0][1], recorder.keep
+        st.launches_per_step = rec.plan.info()["launches"]
+        return True
+
+    def _forward_planned(self, x, output_process, mode):
+        st = self._splan
+        n, c, h, w = x.shape
+        dev, dt = x.device, self.unet.compute_dtype
+        inf = self.diffusion_inf
+        steps, npx = inf.timesteps, n * h * w
+        f32 = dict(dtype=torch.float32, device=dev)
+        cache = self.unet.prepared(dt)
+        table = inf.step_table_device(dev)
+        gammas = inf.gammas.detach().to(**f32).contiguous()
+        for k in [k for k, r in st.plans.items() if r.cache is not cache]:       # plans of an earlier weight generation
+            del st.plans[k]
+        args = ((n, c, h, w), dt, dev, mode, cache, table, gammas)
+        sig = self._plan_sig(*args)
+        rec = st.plans.get(sig)
+        if rec is None:
+            while len(st.plans) >= st.MAX_PLANS:
+                st.plans.popitem(last=False)                                      # the least recently used one
+            rec = st.plans[sig] = _StepPlan()
+            rec.sig, rec.cache, rec.warmed, rec.plan, rec.keep = sig, cache, False, None, None
+            rec.consts = (table, gammas)            # the plan's launches hold their addresses
+            rec.xy = torch.empty(n, h, w, 2 * c, dtype=dt, device=dev)
+            rec.y, rec.gamma_next = torch.empty(npx, c, **f32), torch.empty(n, **f32)
+            rec.pos = torch.empty(1, dtype=torch.int32, device=dev)
+            rec.noise_stack = torch.empty(steps + 1, npx * c, **f32) if mode == "noise" else None
+        else:
+            st.plans.move_to_end(sig)
+
+        def nchw(pixels):           # always a copy: rec.y is rewritten by the next call
+            if c == 1:
+                return pixels.reshape(n, 1, h, w).clone()
+            return pixels.reshape(n, h, w, c).permute(0, 3, 1, 2).clone(memory_format=torch.contiguous_format)
+
+        rng = self.device_rng if mode == "rng" else None
+        if rng is not None:         # y_T: draw 0 of this sampling call, the step read from the generator's device mirror
+            ops.philox_fill_dev(ops.PHILOX_NORMAL, rec.y, rng.seed, 0, ops.STREAM_SAMPLER, rng.device_step(dev))
+        else:                       # tests and fixtures: the 1 + steps draws of noise_fn, stacked once per call
+            rec.noise_stack.copy_(torch.stack([self._noise(k, (n, c, h, w), dev).reshape(-1) for k in range(steps + 1)]))
+            rec.y.copy_(rec.noise_stack[0].reshape(npx, c))
+        process = [nchw(rec.y)] if output_process else None
+        rec.xy.copy_(nnops.to_nhwc(torch.cat([x.to(torch.float32), nchw(rec.y)], dim=1), dt))
+        rec.gamma_next.copy_(gammas[steps - 1].expand(n))
+        ops.counter_set(rec.pos, 1)
+        step_args = (dt, n, npx, c, table, gammas, mode, dev)
+        every = max(steps // 7, 1)
+        for i in reversed(range(steps)):
+            if rec.plan is not None:
+                rec.plan.run()
+                st.replays += 1
+            elif not rec.warmed or st.sticky:
+                # the first step at this signature creates descriptors and may grow the workspace: it is not recorded
+                self._plan_step(rec, *step_args)
+                rec.warmed = True
+            else:
+                now = self._plan_sig(*args)
+                if now != sig:                                                     # the warm-up step grew a registered buffer
+                    st.plans[now] = st.plans.pop(sig)
+                    sig = rec.sig = now
+                self._plan_record(rec, *step_args)
+            if output_process and i % every == 0:
+                process.append(nchw(rec.y))
+        out = nchw(rec.y)
+        if rng is not None:
+            rng.advance()
+        if output_process:
+            return out, torch.stack(process, dim=1)
+        return out
+
+    def sampler_plan_info(self) -> dict:
+        """The state of the planned sampler, in the spirit of ``PlannedStep.describe()``: ``disabled`` is None while calls run
+        from plans, otherwise the reason why they run eagerly."""
+        st = self._splan
+        return {"plans": sum(1 for r in st.plans.values() if r.plan is not None), "records": st.records, "replays": st.replays,
+                "disabled": st.disabled, "launches_per_step": st.launches_per_step}
 
     def configure_optimizers(self):
         raise NotImplementedError("Palette under the Lightning loop is sampling only; train with make_optimizers() / fit_step() "

@@ -1415,3 +1415,56 @@ def palette_step_rng(dtype, model_out, y_t, pixels, C_, learn_var, add_noise, sc
                                           int(bool(learn_var)), int(bool(add_noise)), s1, rs, c0, c1, llo, lhi, _u64(seed),
                                           _u32(sub, "sub"), _u32(step, "step"), _p(y_next, torch.float32), _p(xy_next, dtype),
                                           _stream()), "pai_palette_step_rng")
+
+
+# ---- device-held step state of the planned sampler (csrc/philox.hip, csrc/palette.hip) --------------------------------------------
+# A counter is one int32 device element holding the bits of a uint32 (torch has no arithmetic on unsigned 32-bit tensors,
+# and none is needed: only the kernels read it).
+def counter_set(counter, value):
+    """*counter = value (uint32) in stream order (pai_counter_set)."""
+    L.check(L.load().pai_counter_set(_p(counter, torch.int32), _u32(value, "value"), _stream()), "pai_counter_set")
+
+
+def counter_add(counter, delta=1):
+    """*counter += delta, wrapping at 2^32, in stream order (pai_counter_add)."""
+    L.check(L.load().pai_counter_add(_p(counter, torch.int32), _u32(delta, "delta"), _stream()), "pai_counter_add")
+
+
+def philox_fill_dev(kind, out, seed, sub, stream, step_dev, param=0):
+    """``philox_fill`` with the step read from the device counter ``step_dev`` (pai_philox_fill_dev)."""
+    L.check(L.load().pai_philox_fill_dev(int(kind), _p(out, PHILOX_DTYPES.get(int(kind), torch.int32)), int(out.numel()),
+                                         _u64(seed), _u32(sub, "sub"), _u32(stream, "stream"), _p(step_dev, torch.int32),
+                                         _u32(param, "param"), _stream()), "pai_philox_fill_dev")
+
+
+def palette_step_dev(dtype, model_out, y_t, noise_stack, pixels, C_, learn_var, table, pos, gammas, N, gamma_next, y_next,
+                     xy_next=None):
+    """``palette_step`` of the reverse step whose 1-based index is the device counter ``pos``: the scalars are row
+    ``T - pos`` of ``table`` (fp32 [T][6]), the noise row ``pos`` of ``noise_stack`` (fp32 [T + 1][pixels * C]); also writes
+    ``gamma_next`` [N], the noise level of the next U-Net pass, from ``gammas`` fp32 [T] (pai_palette_step_dev)."""
+    f32 = torch.float32
+    T = int(table.shape[0])
+    if table.dim() != 2 or table.shape[1] != 6 or not table.is_contiguous() or gammas.numel() != T:
+        raise PaiError("palette_step_dev: table is a contiguous [T][6] tensor and gammas has T elements")
+    if noise_stack.numel() != (T + 1) * int(pixels) * int(C_) or gamma_next.numel() < int(N):
+        raise PaiError("palette_step_dev: noise_stack is [T + 1][pixels * C] and gamma_next holds N elements")
+    L.check(L.load().pai_palette_step_dev(code_of(dtype), _p(model_out, dtype), _p(y_t, f32), _p(noise_stack, f32), int(pixels),
+                                          int(C_), int(bool(learn_var)), _p(table, f32), T, _p(pos, torch.int32), _p(gammas, f32),
+                                          int(N), _p(gamma_next, f32), _p(y_next, f32), _p(xy_next, dtype), _stream()),
+            "pai_palette_step_dev")
+
+
+def palette_step_rng_dev(dtype, model_out, y_t, pixels, C_, learn_var, table, pos, gammas, N, gamma_next, seed, rng_step, y_next,
+                         xy_next=None):
+    """``palette_step_dev`` with the noise of draw ``pos`` of the sampling call ``*rng_step`` formed inside the launch
+    (pai_palette_step_rng_dev)."""
+    f32 = torch.float32
+    T = int(table.shape[0])
+    if table.dim() != 2 or table.shape[1] != 6 or not table.is_contiguous() or gammas.numel() != T:
+        raise PaiError("palette_step_rng_dev: table is a contiguous [T][6] tensor and gammas has T elements")
+    if gamma_next.numel() < int(N):
+        raise PaiError("palette_step_rng_dev: gamma_next holds N elements")
+    L.check(L.load().pai_palette_step_rng_dev(code_of(dtype), _p(model_out, dtype), _p(y_t, f32), int(pixels), int(C_),
+                                              int(bool(learn_var)), _p(table, f32), T, _p(pos, torch.int32), _p(gammas, f32),
+                                              int(N), _p(gamma_next, f32), _u64(seed), _p(rng_step, torch.int32),
+                                              _p(y_next, f32), _p(xy_next, dtype), _stream()), "pai_palette_step_rng_dev")
