@@ -246,6 +246,10 @@ class ConvBNAct(torch.autograd.Function):
             C2 = x2.shape[3]
         Cin = C1 + C2
         Cout, _, k, _ = weight.shape
+        if out_f32 and (bn is not None or act not in (ACT_NONE, ACT_TANH)):
+            # the backward pass of the fp32 store knows tanh and the identity only (any other activation's derivative would be
+            # dropped), and a BatchNorm block stores in the storage dtype
+            raise ops.PaiError("ConvBNAct: an fp32 output takes no BatchNorm and tanh or no activation")
         # grouped 3x3 (ResNeXt): block-diagonal dense packs + the groups hint (16-channel slices skip the zero blocks)
         hint = _groups_hint(groups, k, Cin, Cout)
         d = ops.make_desc(dtype, 0, N, H, W, C1, C2, Cout, 1, 0, 0, act if bn is None else ACT_NONE, kernel=k,
