@@ -74,7 +74,9 @@ const char* pai_last_error(void);
  * ran it as bf16); the train-mode Palette U-Net pass (pai_avgpool2_bwd, pai_silu_bwd: additions, the number the library
  * already reported stays).  Also added under 141, no version change: the first layer's weight gradient in the store of the
  * next layer's input gradient (pai_conv_dgrad_act_wthin, _ok, _slab_bytes, _kernel_name; tunables "dgrad_wthin",
- * "wthin_slabs") -- ask for the symbol, not for a number. */
+ * "wthin_slabs") -- ask for the symbol, not for a number.  Likewise the deterministic mode: tunable "deterministic",
+ * pai_conv_wgrad_order_free, pai_conv_dgrad_act_wthin_order_free, pai_order_dependent_launches, pai_get_tunable,
+ * pai_colsum_scratch_bytes, pai_gate_scratch_bytes. */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -88,6 +90,30 @@ int pai_device_info(int* cu_count, int* lds_bytes, char* arch_name, int arch_nam
  * tests that pin the kernel a call runs and for A/B timing in one process; production code never needs it. */
 #define PAI_TUNABLE_UNSET (-2147483647 - 1)
 int pai_set_tunable(const char* name, int value);
+/* The value a switch has now: what pai_set_tunable set, else PAI_TUNE_<name> of the environment, else default_value. */
+int pai_get_tunable(const char* name, int default_value);
+
+/* Deterministic mode: tunable "deterministic" (default 0; PAI_TUNE_deterministic=1 in the environment).  With it 0 every
+ * launch, kernel choice, workspace size and output bit is what it is without the switch.  With it 1 no result depends on
+ * the order in which workgroups, waves or atomics arrive: float sums that cross workgroups go through partial tiles, slabs
+ * or rows written with plain stores and added in a fixed association (the losses: terms rounded so that fp64 addition is
+ * exact), and a launch that cannot do so FAILS -- a missing or too small workspace is an error that names the bytes wanted,
+ * never the atomic path.  Set it BEFORE workspaces are sized: pai_conv_wgrad_workspace_bytes and pai_conv_scratch_bytes
+ * answer for the current value (never less than with it 0).  Stream contract under the mode: ALL weight-gradient calls of a
+ * device are ordered with respect to each other (one stream) -- the partial rows of the bias gradients live in the tail of
+ * the weight-gradient workspace, behind the slabs of the launch they belong to, and pai_colsum uses the head of the
+ * scratch buffer like the forward / input-gradient calls, and so does pai_gate_hidden_bwd.  Byte rule for the scratch
+ * buffer under the mode: register at least
+ *   max(head) + max(tail),   head = pai_conv_scratch_bytes(desc, 0 | 1), pai_colsum_scratch_bytes, pai_gate_scratch_bytes
+ *                            tail = pai_conv_scratch_bytes(desc, 2)
+ * over every call that will run; the calls check their own bytes only, so a buffer smaller than that sum lets a head user on
+ * the main stream and a weight gradient on its stream overlap without an error.  The weight-gradient workspace is used in
+ * whole floats (a byte count that is no multiple of 4 is rounded down).  The loss and metric sums are order-free within
+ * limits the device does not check (see the losses and pai_ssim_sse below).  Not covered: multi-device reductions
+ * (pai_allreduce) keep the order of the communication library.
+ * pai_order_dependent_launches: process-wide count of launches that took an arrival-order path, incremented on the host at
+ * the launch site; it stays put over any run under the mode. */
+int64_t pai_order_dependent_launches(void);
 
 /* ---------------------------------------------------------------------------
  * Convolution family.  One descriptor serves Conv2d and ConvTranspose2d.
@@ -209,6 +235,12 @@ int64_t pai_conv_scratch_bytes(const pai_conv_desc* d, int op);
  * be ordered with respect to each other (the engine issues them on one side stream). */
 int pai_set_wgrad_workspace(void* device_memory, int64_t bytes);
 int64_t pai_conv_wgrad_workspace_bytes(const pai_conv_desc* d);
+/* 1 when pai_conv_wgrad of this layer (has_dbias: with a bias gradient), under the current tunables and the registered
+ * workspaces of the current device, sums nothing across workgroups in arrival order: un-split launches with one writer per
+ * element, slabs + the slab sum, partial blocks.  0 for pixel splits that meet by atomics, for bias sums that do, for the
+ * thin and row-dot forms.  Host only, no device needed (without one: no workspace).  Always 1 under the deterministic
+ * mode, where the launch itself refuses what it cannot honour. */
+int pai_conv_wgrad_order_free(const pai_conv_desc* d, int has_dbias);
 
 /* y = conv(act(x1|x2), w) + bias.
  *   w_fwd   : fwd pack, storage dtype
@@ -267,6 +299,9 @@ int pai_conv_dgrad_act(const pai_conv_desc* d, const void* dy, const void* w_dgr
  * of layers and when the tunable "dgrad_wthin" is 0; the call refuses every pair the predicate refuses for its shape.
  * pai_conv_dgrad_act_wthin_kernel_name: the symbol of the main launch, as pai_conv_kernel_name. */
 int pai_conv_dgrad_act_wthin_ok(const pai_conv_desc* d, const pai_conv_desc* d_thin, int need_dx);
+/* 0: the workgroups of a slab add with atomics.  Under the deterministic mode pai_conv_dgrad_act_wthin_ok answers 0 (the
+ * caller runs pai_conv_dgrad_act and pai_conv_wgrad) and the call itself refuses. */
+int pai_conv_dgrad_act_wthin_order_free(const pai_conv_desc* d, const pai_conv_desc* d_thin);
 int64_t pai_conv_dgrad_act_wthin_slab_bytes(const pai_conv_desc* d, const pai_conv_desc* d_thin);
 int pai_conv_dgrad_act_wthin_kernel_name(const pai_conv_desc* d, const pai_conv_desc* d_thin, char* name, int name_len);
 int pai_conv_dgrad_act_wthin(const pai_conv_desc* d, const void* dy, const void* w_dgrad, const void* a1, int act1,
@@ -541,6 +576,9 @@ int pai_bn_stats_rows(int64_t M);
 int pai_bn_stats(int dtype, const void* z, int64_t M, int C, float* stats, void* stream);
 /* out[C] += column sums of x [rows][C] (storage dtype), e.g. the gradient of a broadcast addend. */
 int pai_colsum(int dtype, const void* x, int64_t rows, int C, float* out, void* stream);
+/* Deterministic mode: pai_colsum stores one partial row per row block into the HEAD of the registered scratch buffer and
+ * adds the rows in order (pai_reduce_rows' kernel); it fails when fewer than these bytes are registered. */
+int64_t pai_colsum_scratch_bytes(int64_t rows, int C);
 
 /* ---------------------------------------------------------------------------
  * Attention gate of the Attention U-Net skip connections.  Replaces the ATen ops behind
@@ -576,12 +614,20 @@ int pai_gate_hidden_bwd(int dtype, const float* dl, const float* logit, const vo
                         const float* gamma_a, const float* sums_a, const float* w_a, const float* mean_i,
                         const float* rstd_i, const float* mean_s, const float* rstd_s, void* dsum,
                         float* partials_i, float* partials_s, float* dw_a, float* db_a, void* stream);
+/* Deterministic mode: d w_a / d b_a are stored as one partial row per workgroup into the HEAD of the registered scratch
+ * buffer and added in row order; pai_gate_hidden_bwd fails when fewer than these bytes are registered. */
+int64_t pai_gate_scratch_bytes(int64_t M, int K);
 
 /* ---------------------------------------------------------------------------
  * Losses.  Replace F.binary_cross_entropy_with_logits / F.l1_loss / F.mse_loss
  * at models/wrapper.py:45-49,66,84-93.  Each accumulates
  * `loss_scale * mean-reduced loss` into *loss (fp64 device scalar, += ) and,
  * when grad != NULL, writes grad = grad_scale * d(mean loss)/d(input).
+ * Deterministic mode: every workgroup's term (loss_scale / numel x the sum over its share of the elements) is rounded to
+ * a multiple of 2^-36 before it is added, so that the fp64 additions are exact in every order.
+ * LIMIT, not checked on the device: the term must be below 256 and *loss must stay below 131072 in magnitude; a term of
+ * 256 or more is added as it is and that launch's sum depends on the arrival order again.  A mean-reduced loss with
+ * |loss_scale| x (largest per-element loss) below 256 always meets the first condition.
  * ------------------------------------------------------------------------- */
 int pai_bce_logits(const float* logits, int64_t numel, float target, float loss_scale,
                    double* loss, float grad_scale, float* grad, void* stream);
@@ -648,6 +694,10 @@ int pai_denormalize(const float* x, const float* grad_out_or_null, int64_t numel
  * allocations are padded to a multiple of 4 bytes: they are written as whole 32-bit words, merged atomically where a word
  * straddles two rows (W % 4 != 0).  NC <= 65535.  Depth strips: a contiguous [N][C][H][W] tensor with H % 16 == 0 is
  * [N*C*16][H/16][W].  pai_eval_kernel_name: symbol of the kernel behind op 0 (pai_eval_planes), as pai_conv_kernel_name.
+ * Deterministic mode (pai_ssim_sse and pai_eval_planes): a workgroup's SSIM term is rounded to a multiple of 2^-36 and its
+ * squared-error term to a multiple of 2^-28 before the fp64 addition, which is then exact in every order.  LIMITS, not
+ * checked on the device: at most 131072 planes per SSIM accumulator; a squared-error term below 65536 (always so for
+ * denormalised images: <= 8 tiles of 1024 pixels with an error of at most 1) and an accumulated squared error below 2^25.
  * ------------------------------------------------------------------------- */
 int pai_ssim_sse(const float* pred, const float* target, int NC, int H, int W, int denorm,
                  double* out2, double* per_image, float* full_map, void* stream);

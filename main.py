@@ -3,10 +3,12 @@
 
 Added (build-only) flags: --synthetic N (train on N synthetic pairs instead of a YAML list),
 --image-size, --num-workers, --device-cache (decode every file once, keep the resized uint8 images in device memory
-and assemble each batch there; falls back to the host loader when the data set does not fit).  Multi-GPU: launch with
+and assemble each batch there; falls back to the host loader when the data set does not fit), --deterministic
+(pai.set_deterministic: run-to-run bit equality of the training step, one device).  Multi-GPU: launch with
 ``python -m torch.distributed.run --nproc-per-node N main.py ...`` (one process per GPU, RCCL).
 """
 import argparse
+import os
 import pathlib
 from argparse import ArgumentParser
 
@@ -25,6 +27,11 @@ HIP_MODELS = ("pix2pix", "attention_unet", "res18_unet", "res50_unet", "resv2_un
 
 
 def main(hparams):
+    if hparams.deterministic:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--deterministic covers one device: a data-parallel run adds the ranks' gradients in the "
+                             "communication library's order")
+        pai.set_deterministic(True)      # before the models are built: their workspaces are sized for the mode
     channel_mults = [int(x) for x in hparams.channel_mults.split(",")]
     if hparams.model == "pix2pix":
         model = pai.Pix2Pix(in_channels=1, out_channels=1, channel_mults=channel_mults,
@@ -113,6 +120,9 @@ def build_parser():
                         help="keep the decoded, resized data set in device memory and build every batch on the GPU")
     parser.add_argument("--image-size", default=256, type=int)
     parser.add_argument("--num-workers", default=0, type=int)
+    parser.add_argument("--deterministic", default=False, action="store_true",
+                        help="same bits on every run: no sum of the library depends on the arrival order of workgroups or "
+                             "atomics (slower; one device)")
     return parser
 
 

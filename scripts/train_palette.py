@@ -17,7 +17,8 @@ torch's generator; the checkpoint then also holds the generator's two integers (
 model, optimizer, scheduler, step count and that state and trains on to ``--steps``; with the device generator the draws of
 step k are the same whether or not the run was interrupted before it.  The batches are not: the checkpoint holds the epoch
 count, not the position inside an epoch, so a run resumed away from an epoch boundary starts a new epoch.  A checkpoint that
-holds rng state is resumed with ``--device-rng`` only.
+holds rng state is resumed with ``--device-rng`` only.  ``--deterministic`` adds ``pai.set_deterministic(True)``: together with
+``--device-rng`` a run resumed at an epoch boundary ends in the bits of the uninterrupted one.
 """
 import argparse
 import os
@@ -58,6 +59,11 @@ def build_parser():
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--device-rng", default=False, action=argparse.BooleanOptionalAction,
                    help="draw inside the kernels from pai.DeviceRNG(--seed); its state goes into the checkpoint")
+    p.add_argument("--deterministic", default=False, action="store_true",
+                   help="pai.set_deterministic: no sum depends on the arrival order of workgroups or atomics; with --device-rng "
+                        "two runs from one seed, or an interrupted and an uninterrupted one, end in the same bits (the shuffle of an "
+                        "epoch is then seeded by (--seed, epoch); without --device-rng torch's generator is left alone and a "
+                        "resumed run sees other batches and draws)")
     p.add_argument("--resume", type=pathlib.Path, help="checkpoint of this script to continue from")
     p.add_argument("--out", type=pathlib.Path, help="checkpoint path (default logs/NAME/palette.ckpt)")
     return p
@@ -71,6 +77,8 @@ def main(args):
         raise SystemExit("give either --synthetic N or -d LIST")
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(args.seed)
+    if args.deterministic:
+        pai.set_deterministic(True)      # before the model is built: its workspaces are sized for the mode
     model = pai.Palette(in_channels=1, out_channels=1, channel_mults=to_tuple(args.channel_mults),
                         attention_res=to_tuple(args.attention_res), dropout=args.dropout, schedule_type=args.schedule,
                         learn_var=args.learn_variance, inference_steps=args.inference_steps).to(dev)
@@ -106,6 +114,12 @@ def main(args):
     while step < args.steps:
         if hasattr(loader, "set_epoch"):
             loader.set_epoch(epoch)
+        if args.deterministic and args.device_rng:
+            # The single-process host loader shuffles from torch's generator: make the order of an epoch a function of (seed,
+            # epoch), so that a run resumed at an epoch boundary sees the batches of the uninterrupted one.  Only with the
+            # device generator, where nothing else of the step draws from torch's: without it t, the noise and the dropout
+            # masks come from this stream, and re-seeding it per epoch would correlate the epochs' draws.
+            torch.manual_seed(args.seed + 1000003 * (epoch + 1))
         seen = 0
         for x, y in loader:
             seen += 1

@@ -15,6 +15,7 @@ from .models.palette import Palette, DiffusionModel, DeviceRNG  # noqa: F401
 from .models.guided_diffusion.unet import UNet  # noqa: F401
 from .models.wrapper import UnetWrapper, Discriminator, DiscriminatorBlock  # noqa: F401
 from .lightning import Trainer, CSVLogger, ModelCheckpoint, LightningModule  # noqa: F401
+from .ops import set_deterministic, is_deterministic  # noqa: F401
 
-__all__ = ["Pix2Pix", "Unet", "AttentionUnetGAN", "AttentionUnet", "ResUnetGAN", "ResUnet", "TransUnetGAN", "TransUnet", "Palette", "DeviceRNG", "UnetWrapper", "Discriminator", "Trainer", "CSVLogger", "ModelCheckpoint",
+__all__ = ["Pix2Pix", "Unet", "AttentionUnetGAN", "AttentionUnet", "ResUnetGAN", "ResUnet", "TransUnetGAN", "TransUnet", "Palette", "DeviceRNG", "set_deterministic", "is_deterministic", "UnetWrapper", "Discriminator", "Trainer", "CSVLogger", "ModelCheckpoint",
            "PaiError", "lib"]

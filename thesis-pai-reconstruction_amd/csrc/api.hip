@@ -44,7 +44,7 @@ static int g_ntunables = 0;
 
 // Default of a tunable from the environment: PAI_TUNE_<name>=<int> (looked up once per name).  For whole-suite A/B runs
 // (pytest, bench.py) of a kernel-selection switch without touching the callers; pai_set_tunable still wins.
-// The code reads 41 tunable names; the cache holds 48 (past that a lookup still works, but calls getenv on every read)
+// The code reads 42 tunable names; the cache holds 48 (past that a lookup still works, but calls getenv on every read)
 // and the set table above 32 at a time.
 struct TunableEnv { char name[32]; int has, value; };
 static TunableEnv g_tunable_env[48];
@@ -87,6 +87,16 @@ extern "C" int pai_set_tunable(const char* name, int value) {
     g_tunables[g_ntunables++].value = value;
     return 0;
 }
+
+// ---- deterministic mode ------------------------------------------------------------------------------------------
+// Launches that took an arrival-order path (float atomics of several workgroups on one address), counted on the host at
+// the launch site: 0 over a run under tunable "deterministic" = 1, which is what keeps a new kernel from bringing such a
+// path back unnoticed.
+static int64_t g_order_dependent = 0;
+void pai_note_order_dependent() { __atomic_fetch_add(&g_order_dependent, 1, __ATOMIC_RELAXED); }
+extern "C" int64_t pai_order_dependent_launches(void) { return __atomic_load_n(&g_order_dependent, __ATOMIC_RELAXED); }
+
+extern "C" int pai_get_tunable(const char* name, int default_value) { return name ? pai_tunable(name, default_value) : default_value; }
 
 static void finish_gg(GG* g);
 
@@ -488,12 +498,17 @@ struct WgradPick {
     int64_t workspace_bytes;    // weight-gradient workspace to register (grouped 3 x 3 partial blocks / pixel-split slabs)
     int64_t scratch_bytes;      // partial tiles of the thin forms
     MfmaPlan mfma;              // valid when wgrad_mfma_ok
+    bool order_free;            // no float sum of this launch crosses workgroups in arrival order (pai_conv_wgrad_order_free)
+    bool colsum_bias;           // deterministic mode: the kernel gets no dbias, the bias gradient is the column sum of dy with
+    int64_t bias_part_bytes;    // its partial rows in the TAIL of the weight-gradient workspace (behind the launch's slabs)
 };
 
 static WgradPick pick_wgrad(int dtype, const GG& g, bool has_dbias, bool has_prologue) {
     WgradPick p = {};
-    const bool grouped = grouped3_wgrad_ok(dtype, g, has_dbias ? (const float*)1 : nullptr), mfma = wgrad_mfma_ok(dtype, g);
-    if (mfma) p.mfma = wgrad_mfma_plan(g, has_dbias, has_prologue);
+    // deterministic mode: the kernels that would add their bias sums atomically run without a bias (kbias), see colsum_bias
+    const bool det = pai_deterministic(), kbias = has_dbias && !det;
+    const bool grouped = grouped3_wgrad_ok(dtype, g, kbias ? (const float*)1 : nullptr), mfma = wgrad_mfma_ok(dtype, g);
+    if (mfma) p.mfma = wgrad_mfma_plan(g, kbias, has_prologue);
     p.part = grouped ? wgrad_slab_acquire(grouped3_wgrad_part_bytes(g)) : nullptr;
     const WgradKernel thin = thin_wgrad_conv_ok(dtype, g) ? WK_THIN_CONV : thin_wgrad_convt_ok(dtype, g) ? WK_THIN_CONVT
                            : thin_wgrad_conv1_ok(dtype, g) ? WK_THIN_CONV1 : thin_wgrad_conv3_ok(dtype, g) ? WK_THIN_CONV3
@@ -505,7 +520,7 @@ static WgradPick pick_wgrad(int dtype, const GG& g, bool has_dbias, bool has_pro
     if (has_prologue) p.k = grouped ? (p.part ? WK_GROUPED3 : WK_NONE) : (wgrad_pro_ok(dtype, g) ? WK_MFMA : WK_NONE);
     else if (p.part) p.k = WK_GROUPED3;     // block-diagonal 3 x 3 filter: the diagonal blocks only (gg_group.hip)
     else if (thin != WK_NONE) p.k = thin;
-    else if (rowdot) p.k = WK_ROWDOT;
+    else if (rowdot && !det) p.k = WK_ROWDOT;     // (its lanes meet by LDS atomics: not under the deterministic mode)
     else p.k = mfma ? WK_MFMA : WK_SIMT;
     p.id = p.k == WK_MFMA && (g.Cout % 128) != 0 ? 3 : wgrad_family[p.k].id;
     p.name = p.k == WK_MFMA ? p.mfma.name : wgrad_family[p.k].name;
@@ -514,6 +529,26 @@ static WgradPick pick_wgrad(int dtype, const GG& g, bool has_dbias, bool has_pro
     p.scratch_bytes = thin == WK_THIN_CONV    ? thin_wgrad_scratch_bytes((int64_t)g.N * g.OHg * g.OWg, g.C1 + g.C2, g.Cout)
                       : thin == WK_THIN_CONV3 ? thin_wgrad_scratch_bytes((int64_t)g.N * g.OHg * g.OWg, 1, g.Cout)
                       : thin != WK_NONE       ? thin_wgrad_scratch_bytes((int64_t)g.N * g.H * g.W, 1, g.Cin) : 0;
+    // The bias gradient of thin_wgrad_k rides on its partial tiles (one writer per element in the mode's second stage); every
+    // other family's is the column sum of dy[N * OH * OW][Cout] -- exactly what their loops add up, tile by tile.
+    const bool thin_bias = p.k == WK_THIN_CONV || p.k == WK_THIN_CONV3;
+    p.colsum_bias = det && has_dbias && !thin_bias;
+    p.bias_part_bytes = det && !thin_bias ? colsum_part_bytes((int64_t)g.N * g.OH * g.OW, g.Cout) : 0;
+    p.workspace_bytes += p.bias_part_bytes;     // (the query knows no dbias: sized for a layer with one)
+    if (det) p.order_free = true;               // a launch that cannot be is refused (conv_wgrad_impl and the launchers)
+    else switch (p.k) {
+        case WK_GROUPED3: p.order_free = true; break;        // partial blocks + a one-writer sum, no bias
+        case WK_MFMA:
+            if (p.mfma.variant < WGRAD_PATCH128) p.order_free = !has_dbias && p.mfma.overwrites;   // un-split, or slabs + the slab sum
+            else p.order_free = p.mfma.ksplit == 1 && !(has_dbias && g.nphase > 1);
+            break;
+        case WK_SIMT: {
+            int rows;
+            p.order_free = wgrad_simt_splits(g, &rows) == 1 && !(has_dbias && g.nphase > 1);
+            break;
+        }
+        default: p.order_free = false; break;   // thin forms (atomics per workgroup, or 16 adders per element) and row-dot
+    }
     return p;
 }
 
@@ -530,6 +565,12 @@ extern "C" int64_t pai_conv_wgrad_workspace_bytes(const pai_conv_desc* d) {
     GG g;
     if (gg_build_fwd(d, &g)) return -1;
     return pick_wgrad(d->dtype, g, false, false).workspace_bytes;
+}
+
+extern "C" int pai_conv_wgrad_order_free(const pai_conv_desc* d, int has_dbias) {
+    GG g;
+    if (!d || gg_build_fwd(d, &g)) return 0;
+    return pick_wgrad(d->dtype, g, has_dbias != 0, false).order_free ? 1 : 0;
 }
 
 extern "C" int64_t pai_conv_workspace_bytes(const pai_conv_desc* d, int op) {
@@ -723,7 +764,14 @@ static const char* pick_wthin(const pai_conv_desc* d, const pai_conv_desc* dt, W
 
 extern "C" int pai_conv_dgrad_act_wthin_ok(const pai_conv_desc* d, const pai_conv_desc* d_thin, int need_dx) {
     WthinPick w;
-    return !need_dx && pai_tunable("dgrad_wthin", 1) && pick_wthin(d, d_thin, &w) == nullptr ? 1 : 0;
+    return !need_dx && pai_tunable("dgrad_wthin", 1) && !pai_deterministic() && pick_wthin(d, d_thin, &w) == nullptr ? 1 : 0;
+}
+
+// Always 0 for a taken launch: several workgroups add into one slab (workgroup % S) by atomics.  Which is why the predicate
+// above answers 0 under the deterministic mode -- callers then run the input gradient and the thin weight gradient apart.
+extern "C" int pai_conv_dgrad_act_wthin_order_free(const pai_conv_desc* d, const pai_conv_desc* d_thin) {
+    (void)d; (void)d_thin;
+    return 0;
 }
 
 extern "C" int64_t pai_conv_dgrad_act_wthin_slab_bytes(const pai_conv_desc* d, const pai_conv_desc* d_thin) {
@@ -748,6 +796,9 @@ extern "C" int pai_conv_dgrad_act_wthin(const pai_conv_desc* d, const void* dy, 
     WthinPick w;
     const char* why = pick_wthin(d, d_thin, &w);
     PAI_CHECK(!why, "pai_conv_dgrad_act_wthin: %s (ask pai_conv_dgrad_act_wthin_ok)", why);
+    PAI_CHECK(!pai_deterministic(), "pai_conv_dgrad_act_wthin: the slabs are added to with atomics -- not under the deterministic mode "
+                                    "(pai_conv_dgrad_act_wthin_ok answers 0 there: pai_conv_dgrad_act + pai_conv_wgrad)");
+    pai_note_order_dependent();
     PAI_CHECK(dy && w_dgrad && a1 && x1 && dw && slabs, "pai_conv_dgrad_act_wthin: null pointer");
     PAI_CHECK((w.T == 2) == (x2 != nullptr), "pai_conv_dgrad_act_wthin: x2 goes with the thin layer's second channel");
     PAI_CHECK(((uintptr_t)x1 & 15) == 0 && ((uintptr_t)x2 & 15) == 0, "pai_conv_dgrad_act_wthin: the thin inputs are read in 16-B chunks");
@@ -933,6 +984,28 @@ static int conv_wgrad_impl(const pai_conv_desc* d, const void* x1, const void* x
     const WgradPick p = pick_wgrad(d->dtype, g, dbias != nullptr, pscale != nullptr);
     PAI_CHECK(p.k != WK_NONE, "pai_conv_wgrad_pro: this layer takes no prologue (ask pai_conv_prologue_ok: the grouped 3 x 3 weight "
                               "gradient needs its workspace, pai_set_wgrad_workspace)");
+    float* bias_rows = nullptr;
+    if (pai_deterministic()) {
+        // every workspace the order-free forms of this launch need, checked before anything is enqueued: the partial tiles of
+        // the thin forms (scratch tail), the pixel-split slabs / partial blocks and, behind them, the bias gradient's partial rows
+        const pai_handle_s* h = pai_ctx();
+        const bool thin = p.k >= WK_THIN_CONV && p.k <= WK_THIN_CONV3T;
+        PAI_CHECK(!thin || (h->scratch && h->scratch_bytes >= p.scratch_bytes),
+                  "pai_conv_wgrad: deterministic mode needs %lld bytes of scratch for the partial tiles of this thin layer "
+                  "(pai_set_scratch; pai_conv_scratch_bytes, op 2)", (long long)p.scratch_bytes);
+        const int64_t dwb = (int64_t)g.Cout * g.wtaps * g.Cin * 4;
+        const int64_t slabs = p.k == WK_GROUPED3 ? grouped3_wgrad_part_bytes(g)
+                              : (p.k == WK_MFMA && p.mfma.variant < WGRAD_PATCH128 && p.mfma.ksplit > 1) ? p.mfma.ksplit * dwb : 0;
+        const int64_t rows = p.colsum_bias ? p.bias_part_bytes : 0;
+        const int64_t have = h->wslab ? h->wslab_bytes & ~(int64_t)3 : 0;      // whole floats: the rows are carved from the rounded end
+        PAI_CHECK(slabs + rows == 0 || have >= slabs + rows,
+                  "pai_conv_wgrad: deterministic mode needs %lld bytes of weight-gradient workspace (%lld for the pixel-split slabs, "
+                  "%lld for the partial rows of the bias gradient; pai_set_wgrad_workspace, pai_conv_wgrad_workspace_bytes)",
+                  (long long)(slabs + rows), (long long)slabs, (long long)rows);
+        // Behind the slabs, and ordered on this stream with the launches that use them: under the mode the weight gradients of a
+        // device are issued on ONE stream (include/pai_hip.h, stream contract), so no concurrent launch writes this tail.
+        if (rows) bias_rows = (float*)((char*)h->wslab + (have - rows));
+    }
     if (overwrite && p.overwrites) {
         a.overwrite = 1;           // every element has exactly one writer: plain stores, nothing to clear
         a.overwrite_bias = p.k != WK_GROUPED3 && overwrite == 1;
@@ -943,6 +1016,11 @@ static int conv_wgrad_impl(const pai_conv_desc* d, const void* x1, const void* x
             e = pai::memset_async(dbias, 0, (size_t)g.Cout * sizeof(float), s);
             PAI_CHECK(e == hipSuccess, "pai_conv_wgrad_overwrite: hipMemsetAsync: %s", hipGetErrorString(e));
         }
+    }
+    if (!p.order_free) pai_note_order_dependent();
+    if (p.colsum_bias) {
+        if (int rc = launch_colsum_det(d->dtype, dy, (int64_t)g.N * g.OH * g.OW, g.Cout, dbias, overwrite != 1, bias_rows, s)) return rc;
+        a.dbias = nullptr;
     }
     switch (p.k) {
         case WK_GROUPED3: return launch_grouped3_wgrad(g, a, p.part, s);

@@ -244,6 +244,16 @@ int launch_fwd_simt(int dtype, const GG& g, const FwdArgs& a, hipStream_t s);
 int launch_fwd_rowdot(int dtype, const GG& g, const FwdArgs& a, hipStream_t s);
 // run-time tunables (pai_set_tunable): kernel-selection switches for A/B timing and for tests that pin a kernel
 int pai_tunable(const char* name, int def);
+// Deterministic mode (tunable "deterministic", default 0): no result may depend on the order in which workgroups, waves or
+// atomics arrive.  A launch site that sums floats across workgroups in arrival order calls pai_note_order_dependent() on the
+// host (pai_order_dependent_launches counts them); under the mode it takes its order-free form or fails with PAI_CHECK.
+static inline bool pai_deterministic() { return pai_tunable("deterministic", 0) != 0; }
+void pai_note_order_dependent();
+// Column sums without atomics (misc.hip): row blocks store partial rows into `part` (colsum_part_bytes), reduce_rows_k adds
+// them in row order.  Also the bias gradient of every convolution family under the mode: out[c] (+)= sum_rows x[row][c].
+int launch_reduce_rows(const float* partial, int rows, int C, float* out, int accumulate, hipStream_t s);
+int64_t colsum_part_bytes(int64_t rows, int C);
+int launch_colsum_det(int dtype, const void* x, int64_t rows, int C, float* out, int accumulate, float* part, hipStream_t s);
 // Selection inside a matrix-core family (gg_mfma.hip, gg_wg3.hip): ONE function decides the variant, its rocprofv3 symbol
 // and the launch geometry; the launcher switches on `variant`, every query (name, rows, bytes) reads a field.
 struct MfmaPlan {
@@ -350,6 +360,7 @@ const char* eval_planes_kernel_name();
 bool wgrad3_ok(const GG& g);
 MfmaPlan wgrad3_plan(const GG& g, bool has_dbias);
 int launch_wgrad3(const GG& g, const WgradArgs& a, const MfmaPlan& p, hipStream_t s);
+int wgrad_simt_splits(const GG& g, int* rows);      // pixel splits of gg_wgrad_simt_k (1 under the deterministic mode) and rows per split
 int launch_wgrad_simt(int dtype, const GG& g, const WgradArgs& a, hipStream_t s);
 int launch_wgrad_rowdot(int dtype, const GG& g, const WgradArgs& a, hipStream_t s);
 int launch_wgrad_mfma(const GG& g, const WgradArgs& a, const MfmaPlan& p, hipStream_t s);

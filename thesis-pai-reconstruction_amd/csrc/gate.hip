@@ -147,14 +147,16 @@ __global__ __launch_bounds__(256) void gate_apply_bwd_k(const T* dout, const T* 
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void gate_hidden_bwd_k(const float* dl, const float* logit, const T* h, const T* ig,
-                                                         const T* sg, int64_t M, int K, const float* mean_a,
-                                                         const float* rstd_a, const float* gamma_a, const float* sums_a,
-                                                         const float* wa, const float* mean_i, const float* rstd_i,
-                                                         const float* mean_s, const float* rstd_s, T* dsum,
-                                                         float* part_i, float* part_s, float* dwa, float* dba,
-                                                         int64_t rows_per_block) {
+// PART (deterministic mode): d w_a / d b_a do not meet by atomics -- workgroup b stores its sums as row b of dwa[blocks][K] and
+// dba[blocks][1] (partial rows like part_i / part_s) and reduce_rows_k adds the rows in order (pai_gate_hidden_bwd).
+template <typename T, bool PART>
+__device__ __forceinline__ void gate_hidden_bwd_body(const float* dl, const float* logit, const T* h, const T* ig,
+                                                     const T* sg, int64_t M, int K, const float* mean_a,
+                                                     const float* rstd_a, const float* gamma_a, const float* sums_a,
+                                                     const float* wa, const float* mean_i, const float* rstd_i,
+                                                     const float* mean_s, const float* rstd_s, T* dsum,
+                                                     float* part_i, float* part_s, float* dwa, float* dba,
+                                                     int64_t rows_per_block) {
     __shared__ float red[256][9];
     const int span = K / 8;
     const int tid = threadIdx.x, kc = (tid % span) * 8, rl = tid / span, lanes = 256 / span;
@@ -210,16 +212,28 @@ __global__ __launch_bounds__(256) void gate_hidden_bwd_k(const float* dl, const 
             if (qn == 0) { part_i[(row + 0) * K + c] = t; part_s[(row + 0) * K + c] = t; }
             else if (qn == 1) part_i[(row + 1) * K + c] = t;
             else if (qn == 2) part_s[(row + 1) * K + c] = t;
+            else if (PART) dwa[(size_t)blockIdx.x * K + c] = t;
             else atomicAdd(dwa + c, t);
         }
         if (qn == 3 && tid == 255 && dba) {
             float t = 0.f;
             for (int l = 0; l < lanes; ++l) t += red[l * span][8];
-            atomicAdd(dba, t);
+            if (PART) dba[blockIdx.x] = t;
+            else atomicAdd(dba, t);
         }
         __syncthreads();
     }
 }
+#define GATE_HB_PARAMS(T)                                                                                                       \
+    const float *dl, const float *logit, const T *h, const T *ig, const T *sg, int64_t M, int K, const float *mean_a,           \
+        const float *rstd_a, const float *gamma_a, const float *sums_a, const float *wa, const float *mean_i,                   \
+        const float *rstd_i, const float *mean_s, const float *rstd_s, T *dsum, float *part_i, float *part_s, float *dwa,       \
+        float *dba, int64_t rows_per_block
+#define GATE_HB_ARGS dl, logit, h, ig, sg, M, K, mean_a, rstd_a, gamma_a, sums_a, wa, mean_i, rstd_i, mean_s, rstd_s, dsum, part_i, part_s, dwa, dba, rows_per_block
+template <typename T> __global__ __launch_bounds__(256) void gate_hidden_bwd_k(GATE_HB_PARAMS(T)) { gate_hidden_bwd_body<T, false>(GATE_HB_ARGS); }
+template <typename T> __global__ __launch_bounds__(256) void gate_hidden_bwd_part_k(GATE_HB_PARAMS(T)) { gate_hidden_bwd_body<T, true>(GATE_HB_ARGS); }
+#undef GATE_HB_PARAMS
+#undef GATE_HB_ARGS
 
 // ---- entry points ---------------------------------------------------------------------------
 static int check_k(int K, const char* what) {
@@ -281,6 +295,10 @@ extern "C" int pai_gate_apply_bwd(int dtype, const void* dout, const void* x, co
     return 0;
 }
 
+extern "C" int64_t pai_gate_scratch_bytes(int64_t M, int K) {
+    return M > 0 && K > 0 ? (int64_t)gate_blocks(M) * (K + 1) * (int64_t)sizeof(float) : -1;
+}
+
 extern "C" int pai_gate_hidden_bwd(int dtype, const float* dl, const float* logit, const void* h, const void* ig,
                                    const void* sg, int64_t M, int K, const float* mean_a, const float* rstd_a,
                                    const float* gamma_a, const float* sums_a, const float* w_a, const float* mean_i,
@@ -293,6 +311,28 @@ extern "C" int pai_gate_hidden_bwd(int dtype, const float* dl, const float* logi
     const int blocks = gate_blocks(M);
     const int64_t rpb = (M + blocks - 1) / blocks;
     hipStream_t s = (hipStream_t)stream;
+    if (pai_deterministic()) {
+        // partial rows in the HEAD of the registered scratch (a main-stream call, like the thin input gradients and pai_colsum)
+        const int64_t need = pai_gate_scratch_bytes(M, K);
+        const pai_handle_s* ctx = pai_ctx();
+        PAI_CHECK(ctx->scratch && ctx->scratch_bytes >= need,
+                  "pai_gate_hidden_bwd: deterministic mode needs %lld bytes of scratch for the partial rows of d w_a / d b_a "
+                  "(pai_set_scratch; pai_gate_scratch_bytes)", (long long)need);
+        float* pw = ctx->scratch;
+        float* pb = pw + (size_t)blocks * K;
+        if (dtype == PAI_F32)
+            PAI_LAUNCH(gate_hidden_bwd_part_k<float>, dim3(blocks), dim3(256), 0, s, dl, logit, (const float*)h,
+                               (const float*)ig, (const float*)sg, M, K, mean_a, rstd_a, gamma_a, sums_a, w_a, mean_i, rstd_i,
+                               mean_s, rstd_s, (float*)dsum, partials_i, partials_s, pw, pb, rpb);
+        else
+            PAI_LAUNCH(gate_hidden_bwd_part_k<bf16_t>, dim3(blocks), dim3(256), 0, s, dl, logit, (const bf16_t*)h,
+                               (const bf16_t*)ig, (const bf16_t*)sg, M, K, mean_a, rstd_a, gamma_a, sums_a, w_a, mean_i,
+                               rstd_i, mean_s, rstd_s, (bf16_t*)dsum, partials_i, partials_s, pw, pb, rpb);
+        PAI_LAUNCH_CHECK();
+        if (int rc = launch_reduce_rows(pw, blocks, K, dw_a, 1, s)) return rc;
+        return db_a ? launch_reduce_rows(pb, blocks, 1, db_a, 1, s) : 0;
+    }
+    if (blocks > 1) pai_note_order_dependent();
     if (dtype == PAI_F32)
         PAI_LAUNCH(gate_hidden_bwd_k<float>, dim3(blocks), dim3(256), 0, s, dl, logit, (const float*)h,
                            (const float*)ig, (const float*)sg, M, K, mean_a, rstd_a, gamma_a, sums_a, w_a, mean_i, rstd_i,

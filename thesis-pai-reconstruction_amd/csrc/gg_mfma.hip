@@ -2075,6 +2075,9 @@ static int wgrad_mfma_splits(const GG& g, bool patch, int tiles, int* rows_out) 
     // bottleneck layers (<= 2048 pixels, 4-8 M weights) those atomics were the whole cost.
     const int unsplit_rows = pai_tunable("wgrad_unsplit_rows", 2048);
     if ((tiles >= 256 && g.M <= unsplit_rows) || (tiles >= 512 && g.M <= 2 * unsplit_rows)) splits = 1;
+    // deterministic mode: un-split as well -- the split launches of these two kernels meet in dW by atomics and have no slab
+    // form (the layers of the training step that split run on gg_wgrad_patch3_k, which has one)
+    if (pai_deterministic()) splits = 1;
     int rows = cdiv(cdiv(g.M, splits), 64) * 64;
     splits = cdiv(g.M, rows);
     *rows_out = rows;

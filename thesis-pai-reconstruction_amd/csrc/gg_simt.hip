@@ -367,15 +367,24 @@ __global__ __launch_bounds__(256) void gg_wgrad_simt_k(GG g, WgradArgs a, int sp
     }
 }
 
-int launch_wgrad_simt(int dtype, const GG& g, const WgradArgs& a, hipStream_t s) {
+// Deterministic mode: un-split.  Every dW element then has ONE adder (a tile per (co, tap, ci) block, the taps of different
+// phases are disjoint), so the atomic add in the store is dw + acc whatever the arrival order; the bias comes from the column
+// sum of dy (conv_wgrad_impl).
+int wgrad_simt_splits(const GG& g, int* rows_out) {
     const int tiles = cdiv(g.Cout, SBM) * cdiv(g.ntaps * g.Cin, SBN) * g.nphase;
-    int splits = cdiv(2048, tiles);
+    int splits = pai_deterministic() ? 1 : cdiv(2048, tiles);
     int max_splits = cdiv(g.M, 64);
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     int rows = cdiv(g.M, splits);
     rows = cdiv(rows, SBK) * SBK;
-    splits = cdiv(g.M, rows);
+    *rows_out = rows;
+    return cdiv(g.M, rows);
+}
+
+int launch_wgrad_simt(int dtype, const GG& g, const WgradArgs& a, hipStream_t s) {
+    int rows;
+    const int splits = wgrad_simt_splits(g, &rows);
     dim3 grid(cdiv(g.Cout, SBM), cdiv(g.ntaps * g.Cin, SBN), g.nphase * splits);
     if (dtype == PAI_F32)
         PAI_LAUNCH(gg_wgrad_simt_k<float>, grid, dim3(256), 0, s, g, a, splits, rows);

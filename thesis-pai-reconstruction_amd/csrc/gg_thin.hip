@@ -1191,6 +1191,51 @@ __global__ __launch_bounds__(256) void thin_wgrad_reduce_k(ThinW p, int T, int n
     }
 }
 
+// The second stage of the deterministic mode: ONE writer per dW / dbias element, so the sum has a fixed association and
+// the store is a plain read-modify-write.  Thread = (element of the folded tile, 1 of 4 slices of ALL partial tiles); the
+// pair form's two column halves (wc and wc + 64 of a partial row) are added inside the thread instead of meeting in dW.
+__global__ __launch_bounds__(256) void thin_wgrad_reduce_det_k(ThinW p, int T, int ntiles, int groups) {
+    __shared__ float red[4][64];
+    const int pst = (16 * T + 1) * 128;
+    const int width = p.pair ? 64 : 128, pe = (16 * T + 1) * width;
+    const int e = blockIdx.x * 64 + (threadIdx.x & 63), slice = threadIdx.x >> 6;
+    const int gy = e / pe, le = e - gy * pe;
+    const int k = le / width, c = le - k * width;
+    float sum = 0.f;
+    if (gy < groups) {
+        const float* src = p.partial + (size_t)gy * pst + k * 128 + c;
+        const size_t bstride = (size_t)groups * pst;
+        int b = slice;
+        for (; b + 28 < ntiles; b += 32) {
+            float t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const float* q = src + (size_t)(b + 4 * u) * bstride;
+                t[u] = p.pair ? q[0] + q[64] : q[0];
+            }
+            sum += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
+        }
+        for (; b < ntiles; b += 4) {
+            const float* q = src + (size_t)b * bstride;
+            sum += p.pair ? q[0] + q[64] : q[0];
+        }
+    }
+    red[slice][threadIdx.x & 63] = sum;
+    __syncthreads();
+    if (slice == 0 && gy < groups) {
+        sum = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+        const int wc = gy * 128 + c;
+        if (wc < p.WC1 + p.WC2) {
+            if (k < 16 * T) {
+                const int tap = k / T, t = k - tap * T;
+                if (tap < p.ntaps) p.dw[(size_t)wc * p.s_wc + tap * p.s_tap + t * p.s_t] += sum;
+            } else if (p.dbias) {
+                p.dbias[wc] += sum;
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void sum1_k(const bf16_t* x, int64_t n, float* out) {
     __shared__ float ws[4];
     float s = 0.f;
@@ -1256,9 +1301,13 @@ static int launch_tw(ThinW& p, int T, hipStream_t s) {
     const int chunks = cdiv(p.M, p.pair ? 128 : 64);
     const int groups = cdiv(p.WC1 + p.WC2, 128);
     const int64_t need = thin_wgrad_scratch_bytes(p.M, T, p.WC1 + p.WC2);
-    const bool no_two = pai_tunable("thin_wgrad_atomic", 0) != 0;   // 1: never two-stage
+    const bool det = pai_deterministic();      // two-stage required, and a second stage with one writer per element
+    const bool no_two = !det && pai_tunable("thin_wgrad_atomic", 0) != 0;   // 1: never two-stage
     const pai_handle_s* ctx = pai_ctx();
     const bool two_stage = !no_two && ctx->scratch != nullptr && ctx->scratch_bytes >= need;
+    // (conv_wgrad_impl has checked the scratch before anything was enqueued and reports the bytes; this only keeps the atomic
+    //  stage unreachable under the mode)
+    PAI_CHECK(!det || two_stage, "launch_tw: deterministic mode without the scratch of the two-stage form");
     int blocks = tw_blocks(p.M, groups, two_stage);
     const int cpb = cdiv(chunks, blocks);
     p.partial = two_stage ? (float*)((char*)ctx->scratch + (ctx->scratch_bytes - need)) : nullptr;
@@ -1267,7 +1316,8 @@ static int launch_tw(ThinW& p, int T, hipStream_t s) {
     PAI_LAUNCH_CHECK();
     if (two_stage) {
         const int elems = groups * (16 * T + 1) * 128;
-        PAI_LAUNCH(thin_wgrad_reduce_k, dim3(cdiv(elems, 64), 16), dim3(256), 0, s, p, T, blocks * 2, groups);
+        if (det) PAI_LAUNCH(thin_wgrad_reduce_det_k, dim3(cdiv(groups * (16 * T + 1) * (p.pair ? 64 : 128), 64)), dim3(256), 0, s, p, T, blocks * 2, groups);
+        else PAI_LAUNCH(thin_wgrad_reduce_k, dim3(cdiv(elems, 64), 16), dim3(256), 0, s, p, T, blocks * 2, groups);
         PAI_LAUNCH_CHECK();
     }
     return 0;

@@ -927,7 +927,8 @@ MfmaPlan wgrad3_plan(const GG& g, bool has_dbias) {
     p.workspace_bytes = ps > 1 ? ps * dw_bytes : 0;
     // pai_conv_wgrad_overwrite needs no zero fill: every dW element has one writer (un-split: the taps of different phases
     // are disjoint) or the slab sum writes it
-    p.overwrites = p.ksplit == 1 || (pai_tunable("wgrad_slab", 1) && wgrad_slab_acquire(p.ksplit * dw_bytes) != nullptr);
+    // (deterministic mode: slabs always -- a launch without them fails in launch_wgrad3 instead of adding atomically)
+    p.overwrites = p.ksplit == 1 || ((pai_deterministic() || pai_tunable("wgrad_slab", 1)) && wgrad_slab_acquire(p.ksplit * dw_bytes) != nullptr);
     // the pipelined K loop (see the kernel): not with a bias gradient (the bias sums live in the round-3 loop only)
     p.db = pai_tunable("wgrad3_pipe", 1) && !has_dbias;
     p.lds = (size_t)2 * (v == WG3_128x64 ? 64 * 256 + 96 * 128 : (v == WG3_64x128 ? 64 * 128 + 96 * 256 : 64 * 256 + 128 * 128));
@@ -940,7 +941,12 @@ int launch_wgrad3(const GG& g, const WgradArgs& a0, const MfmaPlan& p, hipStream
     WgradArgs a = a0;
     const int64_t dwn = (int64_t)g.Cout * g.wtaps * g.Cin;
     float* slab = nullptr;
-    if (p.ksplit > 1 && pai_tunable("wgrad_slab", 1)) slab = wgrad_slab_acquire((int64_t)p.ksplit * dwn * 4);
+    const bool det = pai_deterministic();      // slabs always: the atomic store (MODE 2) is never taken
+    if (p.ksplit > 1 && (det || pai_tunable("wgrad_slab", 1))) slab = wgrad_slab_acquire((int64_t)p.ksplit * dwn * 4);
+    PAI_CHECK(!det || p.ksplit == 1 || slab, "pai_conv_wgrad: deterministic mode needs %lld bytes of weight-gradient workspace for the "
+              "%d pixel-split slabs of this layer (pai_set_wgrad_workspace; pai_conv_wgrad_workspace_bytes)",
+              (long long)p.ksplit * dwn * 4, p.ksplit);
+    PAI_CHECK(!det || !a.dbias, "launch_wgrad3: the bias sums of this kernel meet by atomics (deterministic mode: column sum of dy)");
     a.slab = slab;
     if (a.overwrite_bias && a.dbias) {   // the bias sums of the workgroups meet by atomics
         hipError_t e = pai::memset_async(a.dbias, 0, (size_t)g.Cout * sizeof(float), s);

@@ -3,6 +3,11 @@
 // models/wrapper.py:45-49,66,84-93 and the tanh backward of models/pix2pix.py:216.
 #include "common.h"
 
+// DET (deterministic mode): the workgroup's term is rounded to a multiple of 2^-36 when it is below 2^8, as head_loss_k does
+// (head.hip): such terms add EXACTLY in fp64 while the accumulator stays below 2^17 (36 + 17 = 53 bits), so their sum is the
+// same in every arrival order.  The terms of one accumulator share a sign (losses are sums of non-negative values times one
+// scale), so every partial sum is bounded by the logged total: exact for scaled losses below 131072.
+template <bool DET>
 __device__ __forceinline__ void block_atomic_add(double v, double* dst) {
     __shared__ double wsum[4];
     // wave reduce in double
@@ -11,15 +16,18 @@ __device__ __forceinline__ void block_atomic_add(double v, double* dst) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     if (lane == 0) wsum[wid] = v;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(dst, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    if (threadIdx.x == 0) {
+        double t = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (DET && fabs(t) < 256.0) t = rint(t * 0x1p36) * 0x1p-36;
+        atomicAdd(dst, t);
+    }
 }
 
 enum { L_BCE = 0, L_L1 = 1, L_MSE = 2 };
 
-template <int KIND>
-__global__ __launch_bounds__(256) void loss_k(const float* x, const float* t, float tconst, int64_t numel,
-                                              double loss_scale_over_n, double* loss, float gscale,
-                                              float* grad) {
+template <int KIND, bool DET>
+__device__ __forceinline__ void loss_body(const float* x, const float* t, float tconst, int64_t numel,
+                                          double loss_scale_over_n, double* loss, float gscale, float* grad) {
     double acc = 0.0;
     // L1 / MSE over 16-byte vectors, four per stream in flight per thread, 512 workgroups (launch_loss): every workgroup ends in
     // ONE fp64 atomic on the same address, ~15 ns each -- with 2048 workgroups of one element per thread and iteration the
@@ -50,7 +58,7 @@ __global__ __launch_bounds__(256) void loss_k(const float* x, const float* t, fl
                 if (grad) ((float4*)grad)[i] = make_float4(gs[0], gs[1], gs[2], gs[3]);
             }
         }
-        block_atomic_add(acc * loss_scale_over_n, loss);
+        block_atomic_add<DET>(acc * loss_scale_over_n, loss);
         return;
     }
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < numel; i += (int64_t)gridDim.x * 256) {
@@ -72,7 +80,17 @@ __global__ __launch_bounds__(256) void loss_k(const float* x, const float* t, fl
         acc += (double)l;
         if (grad) grad[i] = g * gscale;
     }
-    block_atomic_add(acc * loss_scale_over_n, loss);
+    block_atomic_add<DET>(acc * loss_scale_over_n, loss);
+}
+template <int KIND>
+__global__ __launch_bounds__(256) void loss_k(const float* x, const float* t, float tconst, int64_t numel,
+                                              double loss_scale_over_n, double* loss, float gscale, float* grad) {
+    loss_body<KIND, false>(x, t, tconst, numel, loss_scale_over_n, loss, gscale, grad);
+}
+template <int KIND>
+__global__ __launch_bounds__(256) void loss_det_k(const float* x, const float* t, float tconst, int64_t numel,
+                                                  double loss_scale_over_n, double* loss, float gscale, float* grad) {
+    loss_body<KIND, true>(x, t, tconst, numel, loss_scale_over_n, loss, gscale, grad);
 }
 
 template <int KIND>
@@ -83,9 +101,16 @@ static int launch_loss(const float* x, const float* t, float tconst, int64_t num
     if (blocks > 2048) blocks = 2048;
     if (KIND != L_BCE && blocks > 512) blocks = 512;      // one same-address fp64 atomic per workgroup (see the kernel)
     if (blocks < 1) blocks = 1;
-    PAI_LAUNCH(loss_k<KIND>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, t, tconst,
-                       numel, (double)loss_scale / (double)numel, loss,
-                       (float)((double)grad_scale / (double)numel), grad);
+    if (pai_deterministic()) {
+        PAI_LAUNCH(loss_det_k<KIND>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, t, tconst,
+                           numel, (double)loss_scale / (double)numel, loss,
+                           (float)((double)grad_scale / (double)numel), grad);
+    } else {
+        if (blocks > 1) pai_note_order_dependent();
+        PAI_LAUNCH(loss_k<KIND>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, t, tconst,
+                           numel, (double)loss_scale / (double)numel, loss,
+                           (float)((double)grad_scale / (double)numel), grad);
+    }
     PAI_LAUNCH_CHECK();
     return 0;
 }

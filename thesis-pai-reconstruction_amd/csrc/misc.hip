@@ -231,19 +231,23 @@ __global__ void reduce_rows_k(const float* partial, int rows, int C, float* out,
     out[c] = accumulate ? out[c] + (float)s : (float)s;
 }
 
-extern "C" int pai_reduce_rows(const float* partial, int rows, int C, float* out, int accumulate,
-                               void* stream) {
-    PAI_CHECK(partial && out, "pai_reduce_rows: null pointer");
-    PAI_LAUNCH(reduce_rows_k, dim3(cdiv(C, 64)), dim3(64), 0, (hipStream_t)stream, partial, rows, C,
-                       out, accumulate);
+int launch_reduce_rows(const float* partial, int rows, int C, float* out, int accumulate, hipStream_t s) {
+    PAI_LAUNCH(reduce_rows_k, dim3(cdiv(C, 64)), dim3(64), 0, s, partial, rows, C, out, accumulate);
     PAI_LAUNCH_CHECK();
     return 0;
 }
 
-// out[c] += sum_rows x[row][c]; block = slab of rows, thread = (channel, row lane)
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_k(const T* x, int64_t rows, int C, int64_t rows_per_block,
-                                                float* out) {
+extern "C" int pai_reduce_rows(const float* partial, int rows, int C, float* out, int accumulate,
+                               void* stream) {
+    PAI_CHECK(partial && out, "pai_reduce_rows: null pointer");
+    return launch_reduce_rows(partial, rows, C, out, accumulate, (hipStream_t)stream);
+}
+
+// out[c] += sum_rows x[row][c]; block = slab of rows, thread = (channel, row lane).  PART: the row blocks do not meet in `out`
+// by atomics -- block b stores its sums as row b of out[gridDim.x][C] (plain stores, one writer per element: blockIdx.y
+// strides over all column chunks) and reduce_rows_k adds the rows in row order (deterministic mode).
+template <typename T, bool PART>
+__device__ __forceinline__ void colsum_body(const T* x, int64_t rows, int C, int64_t rows_per_block, float* out) {
     __shared__ float red[256];
     const int tid = threadIdx.x;
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
@@ -263,13 +267,23 @@ __global__ __launch_bounds__(256) void colsum_k(const T* x, int64_t rows, int C,
         if (tid < width) {
             float t = 0.f;
             for (int l = 0; l < lanes; ++l) t += red[tid + l * width];
-            atomicAdd(out + c0 + tid, t);
+            if (PART) out[(size_t)blockIdx.x * C + c0 + tid] = t;
+            else atomicAdd(out + c0 + tid, t);
         }
         __syncthreads();
     }
 }
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_k(const T* x, int64_t rows, int C, int64_t rows_per_block, float* out) {
+    colsum_body<T, false>(x, rows, C, rows_per_block, out);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_part_k(const T* x, int64_t rows, int C, int64_t rows_per_block, float* part) {
+    colsum_body<T, true>(x, rows, C, rows_per_block, part);
+}
 
-int launch_colsum(int dtype, const void* x, int64_t rows, int C, float* out, hipStream_t s) {
+// launch geometry of both forms: row blocks x column chunks
+static dim3 colsum_grid(int64_t rows, int C, int64_t* rpb_out) {
     int64_t blocks = (rows + 255) / 256;
     if (blocks > 512) blocks = 512;
     if (blocks < 1) blocks = 1;
@@ -278,7 +292,14 @@ int launch_colsum(int dtype, const void* x, int64_t rows, int C, float* out, hip
     int chunks = cdiv(C, 256);
     if (chunks > 64) chunks = 64;
     if (blocks * chunks > 4096) chunks = (int)(4096 / blocks) > 0 ? (int)(4096 / blocks) : 1;
-    const dim3 grid((int)blocks, chunks);
+    *rpb_out = rpb;
+    return dim3((int)blocks, chunks);
+}
+
+int launch_colsum(int dtype, const void* x, int64_t rows, int C, float* out, hipStream_t s) {
+    int64_t rpb;
+    const dim3 grid = colsum_grid(rows, C, &rpb);
+    if (grid.x > 1) pai_note_order_dependent();      // the row blocks meet in `out` by atomics
     if (dtype == PAI_F32)
         PAI_LAUNCH(colsum_k<float>, grid, dim3(256), 0, s, (const float*)x, rows, C, rpb, out);
     else
@@ -287,9 +308,39 @@ int launch_colsum(int dtype, const void* x, int64_t rows, int C, float* out, hip
     return 0;
 }
 
+// The order-free form (deterministic mode; also the bias gradient of every convolution family there): partial rows into
+// `part` (colsum_part_bytes), then reduce_rows_k in row order.  out (+)= the column sums.
+int64_t colsum_part_bytes(int64_t rows, int C) {
+    int64_t rpb;
+    return (int64_t)colsum_grid(rows, C, &rpb).x * C * (int64_t)sizeof(float);
+}
+
+int launch_colsum_det(int dtype, const void* x, int64_t rows, int C, float* out, int accumulate, float* part, hipStream_t s) {
+    int64_t rpb;
+    const dim3 grid = colsum_grid(rows, C, &rpb);
+    if (dtype == PAI_F32)
+        PAI_LAUNCH(colsum_part_k<float>, grid, dim3(256), 0, s, (const float*)x, rows, C, rpb, part);
+    else
+        PAI_LAUNCH(colsum_part_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, rows, C, rpb, part);
+    PAI_LAUNCH_CHECK();
+    return launch_reduce_rows(part, (int)grid.x, C, out, accumulate, s);
+}
+
+extern "C" int64_t pai_colsum_scratch_bytes(int64_t rows, int C) {
+    return rows > 0 && C > 0 ? colsum_part_bytes(rows, C) : -1;
+}
+
 extern "C" int pai_colsum(int dtype, const void* x, int64_t rows, int C, float* out, void* stream) {
     PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "pai_colsum: bad dtype %d", dtype);
     PAI_CHECK(x && out && rows > 0 && C > 0, "pai_colsum: bad arguments");
+    if (pai_deterministic()) {      // partial rows in the HEAD of the registered scratch: a main-stream call, like the thin input gradients
+        const int64_t need = colsum_part_bytes(rows, C);
+        const pai_handle_s* ctx = pai_ctx();
+        PAI_CHECK(ctx->scratch && ctx->scratch_bytes >= need,
+                  "pai_colsum: deterministic mode needs %lld bytes of scratch for the partial rows (pai_set_scratch; pai_colsum_scratch_bytes)",
+                  (long long)need);
+        return launch_colsum_det(dtype, x, rows, C, out, 1, ctx->scratch, (hipStream_t)stream);
+    }
     return launch_colsum(dtype, x, rows, C, out, (hipStream_t)stream);
 }
 

@@ -45,6 +45,11 @@ __device__ __forceinline__ float denorm_val(float v, int denorm) {
     return u != u ? u : fminf(fmaxf(u, 0.f), 1.f);
 }
 
+// DET (deterministic mode): the two terms are rounded so that every fp64 addition into the accumulators is exact and the sums
+// do not depend on the arrival order (as head_loss_k, head.hip).  a -- a workgroup's share of a plane's crop-mean SSIM, |a| <=
+// 1 -- to a multiple of 2^-36 below 2^8: exact while the sum of the |terms| stays below 2^17 (at most one per plane: 131072
+// planes).  b -- a sum of squared errors, >= 0 -- to a multiple of 2^-28 below 2^16: exact while the total stays below 2^25.
+template <bool DET>
 __device__ __forceinline__ void block_add2(double a, double b, double* da, double* db, double* dc) {
     __shared__ double ws[2][4];
 #pragma unroll
@@ -56,8 +61,10 @@ __device__ __forceinline__ void block_add2(double a, double b, double* da, doubl
     if (lane == 0) { ws[0][wid] = a; ws[1][wid] = b; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double sa = ws[0][0] + ws[0][1] + ws[0][2] + ws[0][3];
-        const double sb = ws[1][0] + ws[1][1] + ws[1][2] + ws[1][3];
+        double sa = ws[0][0] + ws[0][1] + ws[0][2] + ws[0][3];
+        double sb = ws[1][0] + ws[1][1] + ws[1][2] + ws[1][3];
+        if (DET && fabs(sa) < 256.0) sa = rint(sa * 0x1p36) * 0x1p-36;
+        if (DET && fabs(sb) < 65536.0) sb = rint(sb * 0x1p28) * 0x1p-28;
         if (da) atomicAdd(da, sa);
         if (dc) atomicAdd(dc, sa);
         if (db) atomicAdd(db, sb);
@@ -162,7 +169,8 @@ __device__ __forceinline__ SsimPix ssim_pix(const float (&vm)[5][4], int j) {
     return q;
 }
 
-// MODE 0: forward metrics.  MODE 1: write the three gradient maps (backward pass 1).
+// MODE 0: forward metrics.  MODE 1: write the three gradient maps (backward pass 1).  MODE 2: MODE 0 with the workgroups'
+// terms rounded for exact addition (deterministic mode, block_add2).
 template <int MODE>
 __global__ __launch_bounds__(256) void ssim_k(const float* pred, const float* target, int H, int W, int denorm,
                                               Gauss gk, double inv_crop, double* out2, double* per_image,
@@ -195,7 +203,7 @@ __global__ __launch_bounds__(256) void ssim_k(const float* pred, const float* ta
         const SsimPix q = ssim_pix(vm, j);
         const float mp = q.mp, mt = q.mt, A1 = q.A1, A2 = q.A2, B1 = q.B1, B2 = q.B2, S = q.S;
         const bool in_crop = y >= PADW && y < H - PADW && x >= PADW && x < W - PADW;
-        if (MODE == 0) {
+        if (MODE != 1) {
             if (full_map) full_map[((size_t)nc * H + y) * W + x] = S;
             if (in_crop) acc += (double)S;
             const float d = P[oy + PADW][ox + PADW] - T[oy + PADW][ox + PADW];
@@ -217,8 +225,8 @@ __global__ __launch_bounds__(256) void ssim_k(const float* pred, const float* ta
         }
     }
     }   // x tiles
-    if (MODE == 0)
-        block_add2(acc * inv_crop, sse, out2, out2 ? out2 + 1 : nullptr, per_image ? per_image + nc : nullptr);
+    if (MODE != 1)
+        block_add2<MODE == 2>(acc * inv_crop, sse, out2, out2 ? out2 + 1 : nullptr, per_image ? per_image + nc : nullptr);
 }
 
 extern "C" int pai_ssim_sse(const float* pred, const float* target, int NC, int H, int W, int denorm,
@@ -233,8 +241,14 @@ extern "C" int pai_ssim_sse(const float* pred, const float* target, int NC, int 
     if (xtiles < 1 || (int64_t)cdiv(H, TS) * NC < 512) xtiles = 1;
     if (xtiles > xt_all) xtiles = xt_all;
     dim3 grid(cdiv(xt_all, xtiles), cdiv(H, TS), NC);
-    PAI_LAUNCH(ssim_k<0>, grid, dim3(256), 0, (hipStream_t)stream, pred, target, H, W, denorm, gk,
-                       inv_crop, out2, per_image, full_map, (float*)nullptr, NC, 0.f, xtiles);
+    if (pai_deterministic()) {
+        PAI_LAUNCH(ssim_k<2>, grid, dim3(256), 0, (hipStream_t)stream, pred, target, H, W, denorm, gk,
+                           inv_crop, out2, per_image, full_map, (float*)nullptr, NC, 0.f, xtiles);
+    } else {
+        if (out2 || per_image) pai_note_order_dependent();
+        PAI_LAUNCH(ssim_k<0>, grid, dim3(256), 0, (hipStream_t)stream, pred, target, H, W, denorm, gk,
+                           inv_crop, out2, per_image, full_map, (float*)nullptr, NC, 0.f, xtiles);
+    }
     PAI_LAUNCH_CHECK();
     return 0;
 }
@@ -280,10 +294,11 @@ __device__ __forceinline__ void store_tile_u8(const TileU8& st, unsigned char* p
     }
 }
 
-__global__ __launch_bounds__(256) void eval_planes_k(const float* pred, const float* target, int H, int W, int denorm,
-                                                     Gauss gk, double inv_crop, double* ssim_plane, double* sse_plane,
-                                                     unsigned char* map_u8, const unsigned char* lut_rgb,
-                                                     unsigned char* hot_u8, int xtiles, int aligned) {
+template <bool DET>
+__device__ __forceinline__ void eval_planes_body(const float* pred, const float* target, int H, int W, int denorm,
+                                                 const Gauss& gk, double inv_crop, double* ssim_plane, double* sse_plane,
+                                                 unsigned char* map_u8, const unsigned char* lut_rgb,
+                                                 unsigned char* hot_u8, int xtiles, int aligned) {
     __shared__ TileIn P, T;
     __shared__ TileH Hb;
     __shared__ __align__(16) TileU8 st[4];                 // SSIM map, R, G, B
@@ -335,10 +350,23 @@ __global__ __launch_bounds__(256) void eval_planes_k(const float* pred, const fl
         }
     }
     // one addition per workgroup and sum, to the words of its own plane
-    block_add2(acc * inv_crop, sse, ssim_plane ? ssim_plane + nc : nullptr, sse_plane ? sse_plane + nc : nullptr, nullptr);
+    block_add2<DET>(acc * inv_crop, sse, ssim_plane ? ssim_plane + nc : nullptr, sse_plane ? sse_plane + nc : nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void eval_planes_k(const float* pred, const float* target, int H, int W, int denorm,
+                                                     Gauss gk, double inv_crop, double* ssim_plane, double* sse_plane,
+                                                     unsigned char* map_u8, const unsigned char* lut_rgb,
+                                                     unsigned char* hot_u8, int xtiles, int aligned) {
+    eval_planes_body<false>(pred, target, H, W, denorm, gk, inv_crop, ssim_plane, sse_plane, map_u8, lut_rgb, hot_u8, xtiles, aligned);
+}
+// deterministic mode: the workgroups of a plane add rounded terms (block_add2)
+__global__ __launch_bounds__(256) void eval_planes_det_k(const float* pred, const float* target, int H, int W, int denorm,
+                                                         Gauss gk, double inv_crop, double* ssim_plane, double* sse_plane,
+                                                         unsigned char* map_u8, const unsigned char* lut_rgb,
+                                                         unsigned char* hot_u8, int xtiles, int aligned) {
+    eval_planes_body<true>(pred, target, H, W, denorm, gk, inv_crop, ssim_plane, sse_plane, map_u8, lut_rgb, hot_u8, xtiles, aligned);
 }
 
-const char* eval_planes_kernel_name() { return "eval_planes_k"; }
+const char* eval_planes_kernel_name() { return pai_deterministic() ? "eval_planes_det_k" : "eval_planes_k"; }
 
 int launch_eval_planes(const float* pred, const float* target, int NC, int H, int W, int denorm, double* ssim_plane,
                        double* sse_plane, unsigned char* map_u8, const unsigned char* lut_rgb, unsigned char* hot_u8,
@@ -350,8 +378,15 @@ int launch_eval_planes(const float* pred, const float* target, int NC, int H, in
     const int xtiles = xt_all < 8 ? xt_all : 8;
     const int aligned = W % 4 == 0 && (((uintptr_t)map_u8 | (uintptr_t)hot_u8) & 3) == 0;
     dim3 grid(cdiv(xt_all, xtiles), cdiv(H, TS), NC);
-    PAI_LAUNCH(eval_planes_k, grid, dim3(256), 0, stream, pred, target, H, W, denorm, gk, inv_crop, ssim_plane, sse_plane,
-               map_u8, lut_rgb, hot_u8, xtiles, aligned);
+    const bool several = grid.x * grid.y > 1 && (ssim_plane || sse_plane);      // workgroups per plane word
+    if (pai_deterministic())
+        PAI_LAUNCH(eval_planes_det_k, grid, dim3(256), 0, stream, pred, target, H, W, denorm, gk, inv_crop, ssim_plane, sse_plane,
+                   map_u8, lut_rgb, hot_u8, xtiles, aligned);
+    else {
+        if (several) pai_note_order_dependent();
+        PAI_LAUNCH(eval_planes_k, grid, dim3(256), 0, stream, pred, target, H, W, denorm, gk, inv_crop, ssim_plane, sse_plane,
+                   map_u8, lut_rgb, hot_u8, xtiles, aligned);
+    }
     PAI_LAUNCH_CHECK();
     return 0;
 }

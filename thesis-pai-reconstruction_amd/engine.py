@@ -358,6 +358,9 @@ class _SideStream:
         which shortens the tail during which the main stream only waits for `join`."""
         if not self.on:
             return torch.cuda.current_stream()
+        if ops.is_deterministic():
+            # ONE weight-gradient stream: the partial rows of the bias gradients share the tail of the weight-gradient workspace
+            return self.fork()
         if self.stream2 is None:
             self.stream2 = torch.cuda.Stream()
         ops.stream_wait_last(self.stream2, torch.cuda.current_stream())

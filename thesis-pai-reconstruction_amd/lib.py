@@ -64,6 +64,8 @@ SIGNATURES = {
     "pai_version": (_I, []),
     "pai_device_info": (_I, [C.POINTER(_I), C.POINTER(_I), C.c_char_p, _I]),
     "pai_set_tunable": (_I, [C.c_char_p, _I]),
+    "pai_get_tunable": (_I, [C.c_char_p, _I]),
+    "pai_order_dependent_launches": (_L, []),
     "pai_create": (_I, [_I, C.POINTER(C.c_void_p)]),
     "pai_bind": (_I, [C.c_void_p]),
     "pai_destroy": (_I, [C.c_void_p]),
@@ -82,10 +84,12 @@ SIGNATURES = {
     "pai_conv_scratch_bytes": (_L, [_D, _I]),
     "pai_set_wgrad_workspace": (_I, [_P, _L]),
     "pai_conv_wgrad_workspace_bytes": (_L, [_D]),
+    "pai_conv_wgrad_order_free": (_I, [_D, _I]),
     "pai_conv_fwd": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pai_conv_dgrad": (_I, [_D, _P, _P, _P, _P, _I, _P]),
     "pai_conv_dgrad_act": (_I, [_D, _P, _P, _P, _P, _P, _I, _P]),
     "pai_conv_dgrad_act_wthin_ok": (_I, [_D, _D, _I]),
+    "pai_conv_dgrad_act_wthin_order_free": (_I, [_D, _D]),
     "pai_conv_dgrad_act_wthin_slab_bytes": (_L, [_D, _D]),
     "pai_conv_dgrad_act_wthin_kernel_name": (_I, [_D, _D, C.c_char_p, _I]),
     "pai_conv_dgrad_act_wthin": (_I, [_D, _P, _P, _P, _I, _P, _I, _D, _P, _P, _P, _P, _I, _P, _L, _P]),
@@ -141,7 +145,9 @@ SIGNATURES = {
     "pai_bn_stats_rows": (_I, [_L]),
     "pai_bn_stats": (_I, [_I, _P, _L, _I, _P, _P]),
     "pai_colsum": (_I, [_I, _P, _L, _I, _P, _P]),
+    "pai_colsum_scratch_bytes": (_L, [_L, _I]),
     "pai_gate_partial_rows": (_I, [_L]),
+    "pai_gate_scratch_bytes": (_L, [_L, _I]),
     "pai_gate_hidden": (_I, [_I, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pai_gate_apply": (_I, [_I, _P, _P, _L, _I, _P, _P, _P, _P, _P]),
     "pai_gate_apply_bwd": (_I, [_I, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _I, _P]),

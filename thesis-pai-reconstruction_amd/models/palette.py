@@ -314,7 +314,8 @@ class Palette(LightningModule):
         rng = self.device_rng if mode == "rng" else None
         return (tuple(shape), dt, dev.index, ops._stream(), bool(self.learn_var), int(table.shape[0]), mode, id(cache),
                 tuple(t.data_ptr() if t is not None else 0 for t in (h.workspace, h.scratch)), table.data_ptr(),
-                gammas.data_ptr(), None if rng is None else (rng.seed, rng.device_step(dev).data_ptr()))
+                gammas.data_ptr(), None if rng is None else (rng.seed, rng.device_step(dev).data_ptr()),
+                ops.is_deterministic())      # a plan replays the launches of the mode it was recorded in
 
     def _plan_step(self, rec, dt, n, npx, c, table, gammas, mode, dev):
         """One reverse step on the static buffers of ``rec``: what is recorded, and what runs un-recorded before that."""

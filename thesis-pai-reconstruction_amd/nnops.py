@@ -953,6 +953,8 @@ class Linear(torch.autograd.Function):
         dtype = x.dtype
         d = ops.make_desc(dtype, 0, 1, 1, M, K, 0, out_f, 1, 0, 0, ACT_NONE, kernel=1)
         ops.ensure_workspace(max(ops.conv_workspace_bytes(d, 0), ops.conv_workspace_bytes(d, 1)), x.device)
+        if ops.is_deterministic():      # the partial rows of the bias gradient (default mode: this weight gradient needs no workspace)
+            ops.ensure_wgrad_workspace([d], x.device)
         wm = weight.detach()
         if dtype == torch.float32:
             wf = wm

@@ -215,6 +215,10 @@ class Handle:
         self.workspace = None
         self.scratch = None
         self.wgrad_workspace = None
+        # deterministic mode: bytes kept free in FRONT of what ensure_scratch is asked for, for the partial rows of
+        # colsum / gate_hidden_bwd (main-stream calls that use the head of the buffer, see reserve_scratch_head)
+        self.scratch_head = 0
+        self._scratch_asked = 0
         # bumped whenever a registered buffer is replaced: a caller's captured hipGraph or a recorded launch
         # plan holds the OLD addresses in its kernel arguments and must not be replayed past such a change
         self.epoch = 0
@@ -235,13 +239,25 @@ class Handle:
 
     def ensure_scratch(self, nbytes: int) -> None:
         """Register (grow) the general scratch buffer (pai_handle_set_scratch)."""
+        self._scratch_asked = max(self._scratch_asked, int(nbytes))
+        nbytes = self._scratch_asked + self.scratch_head
         if nbytes <= 0:
             return
         if self.scratch is None or self.scratch.numel() * 4 < nbytes:
+            if self.scratch is not None and self.scratch_head:
+                torch.cuda.synchronize(self.device)     # side-stream weight gradients may still be using the old tail
             self.scratch = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
             self.epoch += 1
             L.check(L.load().pai_handle_set_scratch(self._h, self.scratch.data_ptr(), self.scratch.numel() * 4),
                     "pai_handle_set_scratch")
+
+    def reserve_scratch_head(self, nbytes: int) -> None:
+        """Deterministic mode: keep ``nbytes`` at the head of the scratch buffer on top of every ``ensure_scratch`` request
+        (which covers head + tail of the convolutions): the partial rows of ``colsum`` / ``gate_hidden_bwd`` then never
+        reach the tail that weight gradients on the side stream are writing."""
+        if nbytes > self.scratch_head:
+            self.scratch_head = int(nbytes)
+            self.ensure_scratch(0)
 
     def ensure_wgrad_workspace(self, nbytes: int) -> None:
         """Register (grow) the weight-gradient slab buffer (pai_handle_set_wgrad_workspace)."""
@@ -521,6 +537,32 @@ def set_tunable(name: str, value: int = TUNABLE_UNSET) -> None:
     L.check(L.load().pai_set_tunable(name.encode(), int(value)), "pai_set_tunable")
 
 
+def get_tunable(name: str, default: int = 0) -> int:
+    """The value a switch has now (pai_get_tunable): set value, else PAI_TUNE_<name>, else ``default``."""
+    return int(L.load().pai_get_tunable(name.encode(), int(default)))
+
+
+def set_deterministic(flag: bool = True) -> None:
+    """Deterministic mode (tunable ``deterministic``, include/pai_hip.h): no result of the library depends on the order in
+    which workgroups, waves or atomics arrive; a launch that cannot honour this raises.  Off by default.  Set it BEFORE
+    models are built: engines size the scratch and weight-gradient workspaces for the mode when they are planned.  Single
+    device only -- a data-parallel run adds its gradients in the communication library's order."""
+    set_tunable("deterministic", 1 if flag else 0)
+
+
+def is_deterministic() -> bool:
+    return get_tunable("deterministic", 0) != 0
+
+
+def order_dependent_launches() -> int:
+    """Process-wide count of launches that summed floats across workgroups in arrival order (pai_order_dependent_launches)."""
+    return int(L.load().pai_order_dependent_launches())
+
+
+def conv_wgrad_order_free(d, has_dbias: bool = False) -> bool:
+    return bool(L.load().pai_conv_wgrad_order_free(C.byref(d), int(bool(has_dbias))))
+
+
 def pack_weights_multi(items):
     """items: [(w_master fp32, Cout, taps, Cin, w_fwd | None, w_dgrad | None)], bf16 packs, Cin and Cout multiples of
     64: every layer in one launch."""
@@ -726,6 +768,8 @@ def bn_stats(dtype, z, M, C_, stats):
 
 def colsum(dtype, x, rows, C_, out):
     """out[C] += column sums of x [rows][C]."""
+    if is_deterministic():      # partial rows in the head of the scratch buffer
+        handle_for(x.device).reserve_scratch_head(L.load().pai_colsum_scratch_bytes(rows, C_))
     L.check(L.load().pai_colsum(code_of(dtype), _p(x), rows, C_, _p(out, torch.float32), _stream()), "pai_colsum")
 
 
@@ -755,6 +799,8 @@ def gate_apply_bwd(dtype, dout, x, att, logit, M, C_, mean_a, rstd_a, dx_skip, d
 
 def gate_hidden_bwd(dtype, dl, logit, h, ig, sg, M, K, mean_a, rstd_a, gamma_a, sums_a, w_a, mean_i, rstd_i,
                     mean_s, rstd_s, dsum, partials_i, partials_s, dw_a, db_a):
+    if is_deterministic():      # partial rows of dw_a / db_a in the head of the scratch buffer
+        handle_for(dl.device).reserve_scratch_head(L.load().pai_gate_scratch_bytes(M, K))
     L.check(L.load().pai_gate_hidden_bwd(code_of(dtype), _p(dl, torch.float32), _p(logit, torch.float32), _p(h),
                                          _p(ig), _p(sg), M, K, _p(mean_a), _p(rstd_a), _p(gamma_a), _p(sums_a),
                                          _p(w_a, torch.float32), _p(mean_i), _p(rstd_i), _p(mean_s), _p(rstd_s),

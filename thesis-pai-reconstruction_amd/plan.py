@@ -189,6 +189,7 @@ class PlannedStep:
             sig.append(opt.plan_state())
         h = ops.handle_for(batch[0].device)
         sig.append(tuple(t.data_ptr() if t is not None else 0 for t in (h.workspace, h.scratch, h.wgrad_workspace)))
+        sig.append(ops.is_deterministic())      # a plan replays the launches of the mode it was recorded in
         return tuple(sig)
 
     # ---- the call -------------------------------------------------------------------------------------------
