@@ -76,7 +76,8 @@ const char* pai_last_error(void);
  * next layer's input gradient (pai_conv_dgrad_act_wthin, _ok, _slab_bytes, _kernel_name; tunables "dgrad_wthin",
  * "wthin_slabs") -- ask for the symbol, not for a number.  Likewise the deterministic mode: tunable "deterministic",
  * pai_conv_wgrad_order_free, pai_conv_dgrad_act_wthin_order_free, pai_order_dependent_launches, pai_get_tunable,
- * pai_colsum_scratch_bytes, pai_gate_scratch_bytes. */
+ * pai_colsum_scratch_bytes, pai_gate_scratch_bytes.  Likewise nn.Dropout2d with the keep flags of the device generator
+ * (pai_dropout2d_rng, pai_dropout2d_rng_dev; stream base PHILOX_STREAM_DROPOUT2D = 4096). */
 int pai_version(void);
 /* Build-option bits.  0 since ABI 130: bit 0 used to announce the round-2 experiment kernels (and pai_pack_frag), which
  * were removed from the library. */
@@ -1008,7 +1009,8 @@ int pai_palette_objective(const float* model_out, const float* noise, const floa
  * Addressing, the same in every entry point: key = (seed low 32 bits, seed high 32 bits), counter = (block, sub, stream,
  * step).  block = flat element index / 4 (/ 8 for keep bits) of the tensor as it lies in memory (NHWC activations, [N][P][C]
  * pixels); sub = 0 except in the sampler, where it is the draw index k (0: y_T, k: the k-th reverse step); stream: 0 = t, 1 = u,
- * 2 = z of the noising, 3 = sampler noise, 16 + i = the dropout of the i-th ResBlock; step = the training step or the index of
+ * 2 = z of the noising, 3 = sampler noise, 16 + i = the dropout of the i-th ResBlock, 4096 + j = the Dropout2d behind decoder j
+ * of a GAN-family U-Net (PHILOX_STREAM_DROPOUT2D; there sub = (rank << 16) | k, see pai_dropout2d_rng); step = the training step or the index of
  * the sampling call, held on the host and passed by value (no device-to-host copy, no synchronisation; the _dev forms at the end
  * of this header read it from a device counter instead).  A tensor that needs
  * more than 2^32 blocks is refused.  Derived values, w a word of the block:
@@ -1083,6 +1085,27 @@ int pai_palette_step_dev(int dtype, const void* model_out, const float* y_t, con
 int pai_palette_step_rng_dev(int dtype, const void* model_out, const float* y_t, int64_t pixels, int C, int learn_var,
                              const float* table, int T, const uint32_t* pos, const float* gammas, int N, float* gamma_next,
                              uint64_t seed, const uint32_t* rng_step, float* y_next, void* xy_next, void* stream_handle);
+
+/* ---------------------------------------------------------------------------
+ * nn.Dropout2d of the GAN families with the keep flags of the device generator (added under ABI 141, no version change).
+ * pai_dropout2d_rng: out[n][p][c] = x[n][p][c] * (keep(n, c) ? keep_scale : 0) on an NHWC tensor, PAI_F32 or PAI_BF16; out may
+ * be x.  The mask is the flat [N][C] tensor of the addressing rule above: element e = n C + c, keep block e / 8, lane e % 8,
+ * counter (block, sub, stream, step), kept iff lane >= thr (thr = round(p 65536)).  C % 8 == 0, so one 8-element vector is one
+ * block; a thread forms the flags of its (n, c0) once and walks the pixels.  The arithmetic after the flags is that of
+ * pai_dropout2d: for the same flags the bits of pai_dropout2d given the mask {0, keep_scale} -- an inf or a NaN is multiplied
+ * by 0, not replaced.  The gradient is the same launch on the gradient with the same tuple; no mask tensor exists.
+ * stream: PHILOX_STREAM_DROPOUT2D (4096) + j for the Dropout2d behind decoder j, clear of the 16 + i of the ResBlocks;
+ * sub = (rank << 16) | k, k the index of the train-mode forward of that network within the step (0: the D-phase forward,
+ * 1: the G-phase forward of a GAN step), rank the data-parallel rank.
+ * pai_dropout2d_rng_dev: the same kernel body with `step` read from *step_dev (the mirror of DeviceRNG.step), so that a
+ * recorded launch stands for every later step.
+ * Refused before any launch: a NULL pointer (step_dev included), a dtype other than the two, C % 8 != 0, N < 1, HW < 1,
+ * thr > 65536, N C / 8 > 2^32. */
+#define PAI_PHILOX_STREAM_DROPOUT2D 4096
+int pai_dropout2d_rng(int dtype, const void* x, int N, int64_t HW, int C, uint64_t seed, uint32_t sub, uint32_t stream,
+                      uint32_t step, uint32_t thr, float keep_scale, void* out, void* stream_handle);
+int pai_dropout2d_rng_dev(int dtype, const void* x, int N, int64_t HW, int C, uint64_t seed, uint32_t sub, uint32_t stream,
+                          const uint32_t* step_dev, uint32_t thr, float keep_scale, void* out, void* stream_handle);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,8 @@
 Added (build-only) flags: --synthetic N (train on N synthetic pairs instead of a YAML list),
 --image-size, --num-workers, --device-cache (decode every file once, keep the resized uint8 images in device memory
 and assemble each batch there; falls back to the host loader when the data set does not fit), --deterministic
-(pai.set_deterministic: run-to-run bit equality of the training step, one device).  Multi-GPU: launch with
+(pai.set_deterministic: run-to-run bit equality of the training step, one device), --device-rng / --rng-seed (nn.Dropout2d
+from the device generator, pai.DeviceRNG: DESIGN.md 7e).  Multi-GPU: launch with
 ``python -m torch.distributed.run --nproc-per-node N main.py ...`` (one process per GPU, RCCL).
 """
 import argparse
@@ -54,6 +55,12 @@ def main(hparams):
             "report.py -m palette evaluates it (DESIGN.md 7c)")
     else:
         raise ValueError(f"Incorrect model name ({hparams.model})")
+    if hparams.device_rng:
+        # Dropout2d flags from the device generator: the step replays from a launch plan and the run resumes to the same bits
+        model.device_rng = pai.DeviceRNG(hparams.rng_seed)
+        if hparams.model == "trans_unet" and hparams.dropout > 0:
+            print("--device-rng: the ViT's token and attention dropout still draw from torch's generator (only nn.Dropout2d is "
+                  "converted); the step runs eagerly")
 
     rank, local, world = pdist.init_from_env()
     device = torch.device("cuda", local)
@@ -123,6 +130,10 @@ def build_parser():
     parser.add_argument("--deterministic", default=False, action="store_true",
                         help="same bits on every run: no sum of the library depends on the arrival order of workgroups or "
                              "atomics (slower; one device)")
+    parser.add_argument("--device-rng", default=False, action="store_true",
+                        help="form the Dropout2d keep flags inside the kernels from pai.DeviceRNG(--rng-seed): a step with dropout "
+                             "replays from a launch plan, and the generator's state goes into the checkpoint")
+    parser.add_argument("--rng-seed", default=0, type=int, help="seed of --device-rng")
     return parser
 
 

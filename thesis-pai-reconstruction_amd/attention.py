@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .engine import GradArena, UnetEngine, _BNState, _Packs, _bn_forward, to_fwd_pack_, wthin_slabs
+from .engine import GradArena, UnetEngine, _BNState, _Packs, _bn_forward, apply_dropout2d, to_fwd_pack_, wthin_slabs
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH
 
 
@@ -188,6 +188,7 @@ class AttentionUnetEngine(UnetEngine):
         S = self.acquire(N, H, W, dtype, x.device)
         P = S["P"]
         S["drop"] = {}
+        self._begin_rng(S, training, x.device)
         xs = x.to(torch.float32)
         xs = xs.contiguous() if Ci == 1 else xs.permute(0, 2, 3, 1).contiguous()
         if dtype == torch.float32:
@@ -314,7 +315,7 @@ class AttentionUnetEngine(UnetEngine):
                 # BatchNorm backward to the two-pass form
                 ops.conv_dgrad_bn(d, G["dsg"][j], wd_s, G["gr"][j - 1], None, S["r"][j - 1], ACT_NONE,
                                   G["gr_raw"][j - 1], ACT_RELU if relu_out else ACT_NONE)
-                ops.dropout2d(dtype, G["gr"][j - 1], S["drop"][j - 1], N, S["dh"][j - 1] * S["dw"][j - 1],
+                apply_dropout2d(dtype, G["gr"][j - 1], S["drop"][j - 1], N, S["dh"][j - 1] * S["dw"][j - 1],
                               self.dec_c[j - 1], G["gr"][j - 1])
                 return None
             return ops.conv_dgrad_bn(d, G["dsg"][j], wd_s, G["gr"][j - 1], None, S["w"][j - 1], ACT_NONE,

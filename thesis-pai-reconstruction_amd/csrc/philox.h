@@ -7,7 +7,9 @@
 //   counter = (block, sub, stream, step)
 //   block   = flat element index / 4 (uniform, normal, integer, raw) or / 8 (keep bits) of the tensor as it lies in memory
 //   sub     = 0, except in the sampler: the draw index k (0 is y_T, k the k-th reverse step)
-//   stream  = PHILOX_STREAM_T | _U | _Z | _SAMPLER, or PHILOX_STREAM_DROPOUT + i for the i-th ResBlock
+//   stream  = PHILOX_STREAM_T | _U | _Z | _SAMPLER, PHILOX_STREAM_DROPOUT + i for the i-th ResBlock of Palette, or
+//             PHILOX_STREAM_DROPOUT2D + j for the Dropout2d behind decoder j of a GAN-family U-Net (there sub = (rank << 16) | k,
+//             k the index of the train-mode forward within the step, and the mask is the flat [N][C] tensor)
 //   step    = the training step or the index of the sampling call, passed by value -- or, in the _dev forms the planned sampler
 //             records, read from a uint32 in device memory (the mirror of DeviceRNG.step)
 // Derived values (fixed: the tests are bit-exact against a host restatement):
@@ -28,6 +30,7 @@ constexpr uint32_t PHILOX_STREAM_U = 1;         // u, the position of gamma betw
 constexpr uint32_t PHILOX_STREAM_Z = 2;         // z of the forward noising
 constexpr uint32_t PHILOX_STREAM_SAMPLER = 3;   // the sampler's y_T and per-step noise
 constexpr uint32_t PHILOX_STREAM_DROPOUT = 16;  // + i: the dropout of the i-th ResBlock
+constexpr uint32_t PHILOX_STREAM_DROPOUT2D = 4096;  // + j: nn.Dropout2d behind decoder j (pai_dropout2d_rng), clear of 16 + i
 
 struct PhiloxKey {
     uint32_t k0, k1;                            // seed low, seed high

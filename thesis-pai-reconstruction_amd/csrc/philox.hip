@@ -122,3 +122,106 @@ extern "C" int pai_philox_fill_dev(int kind, void* out, int64_t n, uint64_t seed
                                    const uint32_t* step_dev, uint32_t param, void* stream_handle) {
     return philox_fill_launch("pai_philox_fill_dev", kind, out, n, seed, sub, stream, 0, step_dev, true, param, stream_handle);
 }
+
+// ---- nn.Dropout2d with the keep flags of the device generator (GAN families) ----------------------------------------------------
+// out[n][p][c] = x[n][p][c] * (keep(n, c) ? keep_scale : 0) on an NHWC tensor.  The mask is the flat [N][C] tensor: the eight
+// channels of a vector are one keep block, block index n * C / 8 + c0 / 8 -- a "column", the same for every pixel of the image.
+// A thread owns one column: it runs the ten rounds once and then walks its pixels, so a 32-byte vector costs a load, eight
+// multiplies and a store.  A workgroup is TC columns x 256 / TC pixels (TC a power of two, chosen on the host so that the lanes
+// of a wave read neighbouring vectors); grid.x strides over the columns, grid.y over the pixels.  The body after the flags is
+// that of dropout2d_k (csrc/misc.hip): for the same flags the bits of pai_dropout2d given the mask {0, keep_scale}.
+template <typename T>
+__device__ __forceinline__ void dropout2d_rng_body(const T* x, int64_t ncol, int CV, int64_t HW, const PhiloxKey& key, uint32_t thr,
+                                                   float keep_scale, int tc_shift, T* out) {
+    const int TC = 1 << tc_shift, TP = 256 >> tc_shift;
+    const int ic = threadIdx.x & (TC - 1), ip = threadIdx.x >> tc_shift;
+    const int64_t C = (int64_t)CV * 8;
+    for (int64_t col = (int64_t)blockIdx.x * TC + ic; col < ncol; col += (int64_t)gridDim.x * TC) {
+        const int64_t n = col / CV;
+        const int64_t base = n * HW * C + (col - n * CV) * 8;
+        const PhiloxBlock blk = philox_block(key, (uint32_t)col);
+        float m[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) m[k] = philox_lane16(blk, k) >= thr ? keep_scale : 0.f;
+        for (int64_t p = (int64_t)blockIdx.y * TP + ip; p < HW; p += (int64_t)gridDim.y * TP) {
+            float v[8];
+            V8<T>::ld(x + base + p * C, v);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] *= m[k];
+            V8<T>::st(out + base + p * C, v);
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void dropout2d_rng_k(const T* x, int64_t ncol, int CV, int64_t HW, PhiloxKey key, uint32_t thr,
+                                                       float keep_scale, int tc_shift, T* out) {
+    dropout2d_rng_body<T>(x, ncol, CV, HW, key, thr, keep_scale, tc_shift, out);
+}
+
+// the same body with counter word 3 read from device memory
+template <typename T>
+__global__ __launch_bounds__(256) void dropout2d_rng_dev_k(const T* x, int64_t ncol, int CV, int64_t HW, PhiloxKey key,
+                                                           const uint32_t* step_dev, uint32_t thr, float keep_scale, int tc_shift,
+                                                           T* out) {
+    key.step = *step_dev;
+    dropout2d_rng_body<T>(x, ncol, CV, HW, key, thr, keep_scale, tc_shift, out);
+}
+
+constexpr int DROPOUT2D_RNG_GRID_X = 4096;      // columns past 4096 workgroups' worth are further trips of the column loop
+
+// the refusals and the launch geometry shared by pai_dropout2d_rng and pai_dropout2d_rng_dev
+static int dropout2d_rng_launch(const char* who, int dtype, const void* x, int N, int64_t HW, int C, uint64_t seed, uint32_t sub,
+                                uint32_t stream, uint32_t step, const uint32_t* step_dev, bool dev, uint32_t thr, float keep_scale,
+                                void* out, void* stream_handle) {
+    PAI_CHECK(x && out, "%s: null pointer", who);
+    PAI_CHECK(!dev || step_dev, "%s: null step counter", who);
+    PAI_CHECK(dtype == PAI_F32 || dtype == PAI_BF16, "%s: dtype=%d", who, dtype);
+    PAI_CHECK(C >= 8 && C % 8 == 0 && N >= 1 && HW >= 1, "%s: bad shape N=%d HW=%lld C=%d", who, N, (long long)HW, C);
+    PAI_CHECK(thr <= 65536u, "%s: thr=%u (round(p 65536), at most 65536)", who, thr);
+    const int CV = C / 8;
+    const int64_t ncol = (int64_t)N * CV;
+    PAI_CHECK(ncol <= (1ll << 32), "%s: mask too large (more than 2^32 blocks of 8)", who);
+    PAI_CHECK(HW <= INT64_MAX / 8 / ncol, "%s: tensor too large N=%d HW=%lld C=%d", who, N, (long long)HW, C);
+    // TC: the columns of one pixel side by side, up to 256; the rest of the workgroup goes over pixels -- unless the image has
+    // fewer pixels than that, where the spare lanes take further columns (HW = 1, the token form, is 256 columns a workgroup)
+    int tc_shift = 0;
+    while ((1 << tc_shift) < CV && tc_shift < 8) ++tc_shift;
+    while (tc_shift < 8 && (256 >> tc_shift) / 2 >= HW) ++tc_shift;
+    const int TC = 1 << tc_shift, TP = 256 >> tc_shift;
+    int64_t gx = (ncol + TC - 1) / TC;
+    if (gx > DROPOUT2D_RNG_GRID_X) gx = DROPOUT2D_RNG_GRID_X;
+    // pixels per thread: as many as leave about two workgroups for each of the 256 compute units
+    int64_t gy = (HW + TP - 1) / TP;
+    const int64_t want = (512 + gx - 1) / gx;
+    if (gy > want) gy = want;
+    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const PhiloxKey key = philox_key(seed, sub, stream, step);
+    hipStream_t s = (hipStream_t)stream_handle;
+    if (dtype == PAI_F32) {
+        if (dev) PAI_LAUNCH(dropout2d_rng_dev_k<float>, grid, dim3(256), 0, s, (const float*)x, ncol, CV, HW, key, step_dev, thr,
+                            keep_scale, tc_shift, (float*)out);
+        else PAI_LAUNCH(dropout2d_rng_k<float>, grid, dim3(256), 0, s, (const float*)x, ncol, CV, HW, key, thr, keep_scale, tc_shift,
+                        (float*)out);
+    } else {
+        if (dev) PAI_LAUNCH(dropout2d_rng_dev_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, ncol, CV, HW, key, step_dev, thr,
+                            keep_scale, tc_shift, (bf16_t*)out);
+        else PAI_LAUNCH(dropout2d_rng_k<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, ncol, CV, HW, key, thr, keep_scale,
+                        tc_shift, (bf16_t*)out);
+    }
+    PAI_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pai_dropout2d_rng(int dtype, const void* x, int N, int64_t HW, int C, uint64_t seed, uint32_t sub, uint32_t stream,
+                                 uint32_t step, uint32_t thr, float keep_scale, void* out, void* stream_handle) {
+    return dropout2d_rng_launch("pai_dropout2d_rng", dtype, x, N, HW, C, seed, sub, stream, step, nullptr, false, thr, keep_scale, out,
+                                stream_handle);
+}
+
+extern "C" int pai_dropout2d_rng_dev(int dtype, const void* x, int N, int64_t HW, int C, uint64_t seed, uint32_t sub,
+                                     uint32_t stream, const uint32_t* step_dev, uint32_t thr, float keep_scale, void* out,
+                                     void* stream_handle) {
+    return dropout2d_rng_launch("pai_dropout2d_rng_dev", dtype, x, N, HW, C, seed, sub, stream, 0, step_dev, true, thr, keep_scale,
+                                out, stream_handle);
+}

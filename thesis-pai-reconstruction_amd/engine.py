@@ -26,7 +26,9 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .nnops import dropout2d_rng_launch
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH
+from .rng import DROPOUT2D_STREAM, dropout_sub
 
 BN_EPS_DEFAULT = 1e-5
 
@@ -384,6 +386,15 @@ class _SideStream:
             ops.stream_wait_last(torch.cuda.current_stream(), self.stream2)
 
 
+def apply_dropout2d(dtype, x, drop, N, HW, C, out):
+    """Dropout2d on an activation or on its gradient, from what the forward kept in its slot: an fp32 [N, C] mask, or
+    ((seed, sub, stream, step_dev), thr, keep_scale) of the device generator."""
+    if isinstance(drop, tuple):
+        dropout2d_rng_launch(dtype, x, N, HW, C, drop[0], drop[1], drop[2], out)
+    else:
+        ops.dropout2d(dtype, x, drop, N, HW, C, out)
+
+
 # --------------------------------------------------------------------------------------
 # generator
 # --------------------------------------------------------------------------------------
@@ -423,18 +434,34 @@ class UnetEngine:
         if self.debug_capture is not None:
             self.debug_capture[name] = t.detach().clone()
 
+    def _begin_rng(self, S, training, device):
+        """With a ``DeviceRNG`` on the network (``unet.device_rng``, set by ``UnetWrapper.device_rng``): the Philox words this
+        forward's Dropout2d sites share -- (seed, sub = (rank << 16) | k, the device mirror of step) -- kept in the slot, so that
+        the backward pass regenerates the flags of ITS forward.  k counts the train-mode forwards since the generator advanced."""
+        S["rng"] = None
+        rng = getattr(self.unet, "device_rng", None)
+        if training and rng is not None:
+            sub = dropout_sub(rng.rank, rng.next_forward())
+            if any(p > 0 for p in self.dec_drop):
+                S["rng"] = (rng.seed, sub, rng.device_step(device))
+
     def _dropout(self, S, j, M, C, dtype):
-        """Training-mode Dropout2d behind decoder j's BatchNorm: S['r'][j] *= mask[n][c] in place; the mask
-        is kept in the slot for the backward pass.  The Bernoulli draw uses torch's device generator."""
+        """Training-mode Dropout2d behind decoder j's BatchNorm: S['r'][j] *= mask[n][c] in place; what the backward pass needs
+        is kept in the slot: the mask, or with a device generator the Philox tuple the flags are rebuilt from (no mask tensor
+        exists then, and every launch is one a plan can replay).  Without either the Bernoulli draw uses torch's device
+        generator.  ``dropout_mask_fn`` wins over the device generator."""
         p = self.dec_drop[j]
         N = S["P"]["N"]
         if self.dropout_mask_fn is not None:
             mask = self.dropout_mask_fn(j, N, C, p, S["r"][j].device).to(torch.float32).contiguous()
+        elif S["rng"] is not None:
+            seed, sub, step_dev = S["rng"]
+            mask = ((seed, sub, DROPOUT2D_STREAM + j, step_dev), ops.dropout_thr(p), 1.0 / (1.0 - p))
         else:
             keep = torch.full((N, C), 1.0 - p, dtype=torch.float32, device=S["r"][j].device)
             mask = torch.bernoulli(keep) / (1.0 - p)
         S["drop"][j] = mask
-        ops.dropout2d(dtype, S["r"][j], mask, N, M // N, C, S["r"][j])
+        apply_dropout2d(dtype, S["r"][j], mask, N, M // N, C, S["r"][j])
 
     # ---- parameters -------------------------------------------------------------------
     def ordered_params(self):
@@ -601,6 +628,7 @@ class UnetEngine:
         S = self.acquire(N, H, W, dtype, x.device)
         P = S["P"]
         S["drop"] = {}
+        self._begin_rng(S, training, x.device)
         xs = x.to(torch.float32)
         xs = xs.contiguous() if Ci == 1 else xs.permute(0, 2, 3, 1).contiguous()
         if dtype == torch.float32:
@@ -755,7 +783,7 @@ class UnetEngine:
         if (j - 1) in S["drop"] or self.dec_bn[j - 1] is None:
             ops.conv_dgrad(d, dh, wd, G["gr"][j - 1], G["gskip"][0])
             if (j - 1) in S["drop"]:
-                ops.dropout2d(dtype, G["gr"][j - 1], S["drop"][j - 1], N, S["dh"][j - 1] * S["dw"][j - 1], self.dec_c[j - 1],
+                apply_dropout2d(dtype, G["gr"][j - 1], S["drop"][j - 1], N, S["dh"][j - 1] * S["dw"][j - 1], self.dec_c[j - 1],
                               G["gr"][j - 1])
         else:
             pst, pbn = S["dbn"][j - 1], self.dec_bn[j - 1]
@@ -797,7 +825,7 @@ class UnetEngine:
             elif (j - 1) in S["drop"]:
                 # producer carries Dropout2d: plain gradient, mask, then the two-pass BatchNorm backward
                 ops.conv_dgrad(d, dz, wd, G["gr"][j - 1], G["gskip"][L - 1 - j])
-                ops.dropout2d(dtype, G["gr"][j - 1], S["drop"][j - 1], N, S["dh"][j - 1] * S["dw"][j - 1],
+                apply_dropout2d(dtype, G["gr"][j - 1], S["drop"][j - 1], N, S["dh"][j - 1] * S["dw"][j - 1],
                               self.dec_c[j - 1], G["gr"][j - 1])
                 fused_rows = None
             else:

@@ -765,6 +765,34 @@ def film_norm_act(x, weight, bias, emb_out=None, *, act="silu", dropout_mask=Non
                               bool(advance_in_backward), rng)
 
 
+def dropout2d(x, p, rng):
+    """``nn.Dropout2d(p)`` in training mode on channels-last memory with the keep flags of the device generator (csrc/philox.h):
+    ``x * (keep(n, c) ? 1 / (1 - p) : 0)``, differentiable.  x: [N, C] (one pixel per sample, the token form), [N, rows, C] or
+    NHWC [N, H, W, C], fp32 or bf16, contiguous, on the device, C a multiple of 8.  rng = (seed, sub, stream, step): the Philox
+    tuple of the flat [N][C] mask; channel c of sample n is kept iff its 16-bit lane >= round(p 65536).  ``step`` is an integer or
+    the device scalar of ``DeviceRNG.device_step`` (then a launch recorded into a plan follows the counter).  The backward
+    regenerates the flags from the same tuple; no mask tensor exists and torch's generator is not touched
+    (``pai_dropout2d_rng`` / ``pai_dropout2d_rng_dev``)."""
+    from . import nnops
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ops.PaiError("dropout2d needs a HIP device tensor (no CPU fallback exists)")
+    if x.dim() not in (2, 3, 4) or x.numel() == 0:
+        raise ops.PaiError(f"dropout2d: x of shape {tuple(x.shape)} ([N, C], [N, rows, C] or [N, H, W, C])")
+    if not x.is_contiguous():
+        raise ops.PaiError("dropout2d: x must be contiguous")
+    ops.code_of(x.dtype)
+    if x.shape[-1] % 8:
+        raise ops.PaiError(f"dropout2d: C={x.shape[-1]} (a multiple of 8)")
+    if not 0.0 <= p < 1.0:
+        raise ops.PaiError(f"dropout2d: p={p}")
+    if rng is None or len(rng) != 4:
+        raise ops.PaiError("dropout2d: rng is (seed, sub, stream, step)")
+    seed, sub, stream, step = rng
+    rng = (ops._u64(seed), ops._u32(sub, "sub"), ops._u32(stream, "stream"), step if torch.is_tensor(step) else ops._u32(step, "step"))
+    n, c = x.shape[0], x.shape[-1]
+    return nnops.Dropout2dRng.apply(x.view(n, 1, -1, c), rng, float(p)).view(x.shape)
+
+
 # --------------------------------------------------------------------------------------
 # Palette training objective: forward noising, MSE + variational bound (differentiable)
 # --------------------------------------------------------------------------------------

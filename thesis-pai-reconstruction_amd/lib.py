@@ -229,6 +229,8 @@ SIGNATURES = {
     # device-held step state of the planned sampler: counters, and the forms that read the step / the step index from them
     "pai_counter_set": (_I, [_P, _U32, _P]),
     "pai_counter_add": (_I, [_P, _U32, _P]),
+    "pai_dropout2d_rng": (_I, [_I, _P, _I, _L, _I, _U64, _U32, _U32, _U32, _U32, _F, _P, _P]),
+    "pai_dropout2d_rng_dev": (_I, [_I, _P, _I, _L, _I, _U64, _U32, _U32, _P, _U32, _F, _P, _P]),
     "pai_philox_fill_dev": (_I, [_I, _P, _L, _U64, _U32, _U32, _P, _U32, _P]),
     "pai_palette_step_dev": (_I, [_I, _P, _P, _P, _L, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "pai_palette_step_rng_dev": (_I, [_I, _P, _P, _L, _I, _I, _P, _I, _P, _P, _I, _P, _U64, _P, _P, _P, _P]),

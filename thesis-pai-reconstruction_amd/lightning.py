@@ -20,6 +20,8 @@ from typing import Any, Dict, List, Optional
 import torch
 import torch.nn as nn
 
+from . import rng as _rng
+
 
 # --------------------------------------------------------------------------------------
 class LightningModule(nn.Module):
@@ -404,6 +406,8 @@ class Trainer:
             "optimizer_states": [_to_cpu(o.state_dict()) for o in opts],
             "callbacks": {type(cb).__name__: cb.state_dict() for cb in self.callbacks if hasattr(cb, "state_dict")},
         }
+        # the device generator's two integers (model.device_rng): with them a resumed run draws the Dropout2d flags it would have
+        ckpt.update(_rng.checkpoint_state(m))
         tmp = str(path) + ".tmp"
         torch.save(ckpt, tmp)
         os.replace(tmp, str(path))
@@ -412,6 +416,7 @@ class Trainer:
         """Load weights, optimizer states, callback states and the step counters saved by ``save_checkpoint``;
         call before ``fit`` (``fit(..., ckpt_path=...)`` does)."""
         ckpt = torch.load(str(checkpoint_path), map_location="cpu", weights_only=False)
+        _rng.restore_checkpoint_state(model, ckpt)      # refuses a generator on one side only, before anything is loaded
         model.load_state_dict(ckpt["state_dict"])
         if self.device is not None:
             model.to(self.device)
@@ -474,6 +479,8 @@ class Trainer:
             ckpt_path=None):
         self.model = model
         model.trainer = self
+        if getattr(model, "device_rng", None) is not None:
+            model.device_rng.rank = self.global_rank     # the ranks of a data-parallel run drop different channels
         if self.device is not None:
             model.to(self.device)
         model.set_precision(self.precision)

@@ -56,8 +56,10 @@ class AttentionUnet(nn.Module):
         self.in_channels, self.out_channels = in_channels, out_channels
         self.channel_mults = tuple(channel_mults)
         self.dropout = dropout
+        self.dropout_is_dropout2d = True    # plan.PlannedStep: this rate only parameterises nn.Dropout2d modules
         self.compute_dtype = torch.float32
         self.bn_updates_per_forward = 1
+        self.device_rng = None      # a DeviceRNG (set through UnetWrapper.device_rng): Dropout2d flags from the kernels
 
         encoders = [nn.Conv2d(in_channels, channel_mults[0] * 64, kernel_size=4, stride=2, padding=1)]
         cin = channel_mults[0] * 64

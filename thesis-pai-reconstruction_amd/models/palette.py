@@ -27,6 +27,7 @@ from .. import functional as PF
 from .. import nnops, ops
 from ..lightning import LightningModule
 from ..ops import PaiError
+from ..rng import DeviceRNG  # noqa: F401  (the class lived here first; pai.DeviceRNG and this name stay the same class)
 from .guided_diffusion.unet import UNet
 from .utils import denormalize, to_int
 
@@ -94,68 +95,6 @@ class DiffusionModel(nn.Module):
             t = torch.tensor(self.step_table(), dtype=torch.float32).to(device)
             d = self._table_dev = (self._versions(), t)
         return d[1]
-
-
-class DeviceRNG:
-    """The state of the device generator (csrc/philox.h): a 64-bit ``seed`` and a ``step`` counter, two Python integers.  Every
-    random value of a Palette step is a pure function of (seed, step, site, element index), so a run resumes reproducibly
-    from ``state_dict()``.  ``step`` is the training step or the index of the sampling call: each consumer calls ``advance()``
-    once per call.  The two integers are the truth (``state_dict`` / ``load_state_dict`` / ``--resume``), and nothing is ever
-    read back from the device.
-
-    A consumer whose launches are replayed from a recorded plan (the planned sampler) cannot take ``step`` by value: it asks
-    ``device_step(device)`` for a uint32 device scalar that mirrors it.  The mirror of a device is created on that first
-    request; from then on ``advance()`` moves it with ``pai_counter_add`` in stream order, and the next request rewrites it
-    with ``pai_counter_set`` whenever the host value is not the one the mirror was last given (first use,
-    ``load_state_dict``, an assignment to ``step``).  Without such a consumer no mirror exists and nothing is launched.  A
-    mirror follows the host in the order of ONE stream: consumers on different streams need generators of their own."""
-
-    def __init__(self, seed: int = 0, step: int = 0):
-        self.seed, self.step = self._check(seed, 64, "seed"), self._check(step, 32, "step")
-        self._mirrors = {}          # device index -> [int32 device scalar (the bits of the uint32), the value it holds]
-
-    @staticmethod
-    def _check(v, bits, what):
-        v = int(v)
-        if not 0 <= v < 1 << bits:
-            raise PaiError(f"DeviceRNG: {what}={v} is not an unsigned {bits}-bit integer")
-        return v
-
-    def advance(self, n: int = 1) -> int:
-        """The step the next call uses; the counter is 32 bits wide and wraps."""
-        old = self.step
-        self.step = (old + int(n)) & 0xFFFFFFFF
-        for m in self._mirrors.values():
-            if m[1] == old:                     # in step with the host: stays so; otherwise the next request rewrites it
-                with torch.cuda.device(m[0].device):
-                    ops.counter_add(m[0], int(n) & 0xFFFFFFFF)
-                m[1] = self.step
-        return self.step
-
-    def device_step(self, device) -> torch.Tensor:
-        """The device scalar (int32 storage, uint32 bits) that holds ``step`` in the order of the current stream of ``device``."""
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise PaiError("DeviceRNG.device_step needs a HIP device")
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        m = self._mirrors.get(idx)
-        if m is None:
-            m = self._mirrors[idx] = [torch.empty(1, dtype=torch.int32, device=torch.device("cuda", idx)), None]
-        step = self._check(self.step, 32, "step")
-        if m[1] != step:
-            with torch.cuda.device(m[0].device):
-                ops.counter_set(m[0], step)
-            m[1] = step
-        return m[0]
-
-    def state_dict(self) -> dict:
-        return {"seed": self.seed, "step": self.step}
-
-    def load_state_dict(self, state) -> None:
-        self.seed, self.step = self._check(state["seed"], 64, "seed"), self._check(state["step"], 32, "step")
-
-    def __repr__(self):
-        return f"DeviceRNG(seed={self.seed}, step={self.step})"
 
 
 def sampler_plan_default() -> bool:

@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from .. import nnops
 from ..ops import ACT_NONE, ACT_RELU, ACT_TANH, PaiError
+from ..rng import DROPOUT2D_STREAM, dropout_sub
 from .wrapper import UnetWrapper
 
 ResType = Literal["18", "50", "v2", "next"]
@@ -194,6 +195,7 @@ class ResUnet(nn.Module):
         self.compute_dtype = torch.float32
         self.bn_updates_per_forward = 1
         self.dropout_mask_fn = None      # tests: fn(j, N, C, p, device) -> fp32 [N, C] of {0, 1 / (1 - p)}
+        self.device_rng = None           # a DeviceRNG (set through UnetWrapper.device_rng): Dropout2d flags from the kernels
         self.debug_capture = None        # tests: dict name -> detached NHWC activation
         self.in_conv = nn.Conv2d(in_channels, 64, kernel_size=3, padding=1)
         cin = 64
@@ -244,6 +246,10 @@ class ResUnet(nn.Module):
             if self.debug_capture is not None:
                 self.debug_capture[f"enc{len(skips) - 1}"] = h.detach().float()
         skips.pop()
+        rng = self.device_rng if self.training else None
+        if rng is not None:
+            # one sub for the sites of this forward: (rank << 16) | k, k the train-mode forwards since the generator advanced
+            rng_sub = dropout_sub(rng.rank, rng.next_forward())
         for j, dec in enumerate(self.decoders):
             if j != 0:
                 h = (h, skips.pop())        # read as cat([h, skip]) by the block's convolutions (two-pointer inputs)
@@ -254,9 +260,15 @@ class ResUnet(nn.Module):
                 n, c = h.shape[0], h.shape[3]
                 if self.dropout_mask_fn is not None:
                     mask = self.dropout_mask_fn(j, n, c, drop.p, h.device).to(torch.float32).contiguous()
+                    h = nnops.Dropout2d.apply(h, mask)
+                elif rng is not None:
+                    # the flags are formed inside the launch and rebuilt by its backward; the step is read from the generator's
+                    # device mirror, so the launch is one a recorded plan can replay
+                    h = nnops.Dropout2dRng.apply(h, (rng.seed, rng_sub, DROPOUT2D_STREAM + j, rng.device_step(h.device)),
+                                                 float(drop.p))
                 else:
                     mask = torch.bernoulli(torch.full((n, c), 1.0 - drop.p, device=h.device)) / (1.0 - drop.p)
-                h = nnops.Dropout2d.apply(h, mask)
+                    h = nnops.Dropout2d.apply(h, mask)
             h = nnops.Upsample2.apply(h)
             if self.debug_capture is not None:
                 self.debug_capture[f"dec{j}"] = h.detach().float()

@@ -30,6 +30,12 @@ class UnetWrapper(LightningModule):
     :param loss_type: one of "gan", "ssim", "psnr", "mse", "ssim+psnr".
     """
 
+    # Opt-in: a ``DeviceRNG``.  Every train-mode Dropout2d site of the generator then forms its keep flags inside a kernel
+    # (pai_dropout2d_rng_dev) from (seed, step, forward index, decoder index) instead of drawing a mask with torch: the step can be
+    # replayed from a launch plan (plan.PlannedStep), and a run resumes to the same bits from the two integers in the checkpoint.
+    # ``training_step`` advances the generator once per call.  None: torch's generator draws the masks, as before.
+    device_rng = None
+
     def __init__(self, unet: nn.Module,
                  loss_type: Literal["gan", "ssim", "psnr", "ssim+psnr", "mse"] = "gan"):
         super().__init__()
@@ -122,6 +128,9 @@ class UnetWrapper(LightningModule):
     def training_step(self, batch, batch_idx):
         """Reference models/wrapper.py:117-162 (manual optimisation, D step then G step)."""
         x, target = batch
+        rng = self.device_rng
+        if getattr(self.unet, "device_rng", None) is not rng:
+            self.unet.device_rng = rng
         reuse = self.loss_type == "gan" and self._can_reuse_forward()
         pred_g = None
         metrics_early = None
@@ -189,6 +198,10 @@ class UnetWrapper(LightningModule):
         self.manual_backward(loss)
         opt_g.step()
         self.untoggle_optimizer(opt_g)
+        if rng is not None:
+            # the next step's flags: the host integer moves, and the device mirror by one pai_counter_add on this stream, behind
+            # the last launch that read it (part of a recorded step)
+            rng.advance()
 
     def validation_step(self, batch, batch_idx):
         """Reference models/wrapper.py:164-173."""

@@ -753,6 +753,41 @@ class Dropout2d(torch.autograd.Function):
         return out, None
 
 
+def dropout2d_rng_launch(dtype, x, N, HW, C, rng, thr, keep_scale, out):
+    """One Dropout2d launch on the flags of ``rng = (seed, sub, stream, step)``: ``step`` an integer (by value) or the int32
+    device scalar of ``DeviceRNG.device_step`` (the _dev form, which a recorded plan replays)."""
+    seed, sub, stream, step = rng
+    if torch.is_tensor(step):
+        ops.dropout2d_rng_dev(dtype, x, N, HW, C, seed, sub, stream, step, thr, keep_scale, out)
+    else:
+        ops.dropout2d_rng(dtype, x, N, HW, C, seed, sub, stream, step, thr, keep_scale, out)
+
+
+class Dropout2dRng(torch.autograd.Function):
+    """nn.Dropout2d in training mode with the keep flags of the device generator: ``apply(x, (seed, sub, stream, step), p)`` on
+    an NHWC tensor.  The backward is the same launch on the gradient with the same tuple: no mask tensor is saved or exists."""
+
+    @staticmethod
+    def forward(ctx, x, rng, p):
+        _check(x)
+        if len(rng) != 4:
+            raise ops.PaiError("Dropout2dRng: rng is (seed, sub, stream, step)")
+        if not 0.0 <= p < 1.0:
+            raise ops.PaiError(f"Dropout2dRng: p={p}")
+        N, H, W, C = x.shape
+        ctx.rng, ctx.thr, ctx.keep_scale = tuple(rng), ops.dropout_thr(p), 1.0 / (1.0 - p)
+        out = torch.empty_like(x)
+        dropout2d_rng_launch(x.dtype, x, N, H * W, C, ctx.rng, ctx.thr, ctx.keep_scale, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        N, H, W, C = g.shape
+        out = torch.empty_like(g)
+        dropout2d_rng_launch(g.dtype, g.contiguous(), N, H * W, C, ctx.rng, ctx.thr, ctx.keep_scale, out)
+        return out, None, None
+
+
 class Fork(torch.autograd.Function):
     """x -> (x, x) for a tensor with two consumers (block input -> residual branch + skip branch, encoder feature ->
     next level + decoder, token stream -> sublayer + its residual; reference models/res_unet.py:165-171,

@@ -1392,6 +1392,7 @@ PHILOX_RAW, PHILOX_UNIFORM, PHILOX_NORMAL, PHILOX_INT, PHILOX_KEEP = 0, 1, 2, 3,
 PHILOX_DTYPES = {PHILOX_RAW: torch.int32, PHILOX_UNIFORM: torch.float32, PHILOX_NORMAL: torch.float32, PHILOX_INT: torch.int32,
                  PHILOX_KEEP: torch.uint8}
 STREAM_T, STREAM_U, STREAM_Z, STREAM_SAMPLER, STREAM_DROPOUT = 0, 1, 2, 3, 16
+STREAM_DROPOUT2D = 4096         # PHILOX_STREAM_DROPOUT2D: + j for the Dropout2d behind decoder j of a GAN-family U-Net
 
 
 def _u64(v, what="seed") -> int:
@@ -1461,6 +1462,21 @@ def palette_step_rng(dtype, model_out, y_t, pixels, C_, learn_var, add_noise, sc
                                           int(bool(learn_var)), int(bool(add_noise)), s1, rs, c0, c1, llo, lhi, _u64(seed),
                                           _u32(sub, "sub"), _u32(step, "step"), _p(y_next, torch.float32), _p(xy_next, dtype),
                                           _stream()), "pai_palette_step_rng")
+
+
+def dropout2d_rng(dtype, x, N, HW, C_, seed, sub, stream, step, thr, keep_scale, out):
+    """out = x * (keep(n, c) ? keep_scale : 0) over an NHWC tensor, the keep flags of the flat [N][C] mask formed inside the launch
+    from the Philox tuple (seed, sub, stream, step) and ``thr = dropout_thr(p)``; out may be x (pai_dropout2d_rng)."""
+    L.check(L.load().pai_dropout2d_rng(code_of(dtype), _p(x, dtype), int(N), int(HW), int(C_), _u64(seed), _u32(sub, "sub"),
+                                       _u32(stream, "stream"), _u32(step, "step"), _u32(thr, "thr"), float(keep_scale),
+                                       _p(out, dtype), _stream()), "pai_dropout2d_rng")
+
+
+def dropout2d_rng_dev(dtype, x, N, HW, C_, seed, sub, stream, step_dev, thr, keep_scale, out):
+    """``dropout2d_rng`` with the step read from the device counter ``step_dev`` (pai_dropout2d_rng_dev)."""
+    L.check(L.load().pai_dropout2d_rng_dev(code_of(dtype), _p(x, dtype), int(N), int(HW), int(C_), _u64(seed), _u32(sub, "sub"),
+                                           _u32(stream, "stream"), _p(step_dev, torch.int32), _u32(thr, "thr"),
+                                           float(keep_scale), _p(out, dtype), _stream()), "pai_dropout2d_rng_dev")
 
 
 # ---- device-held step state of the planned sampler (csrc/philox.hip, csrc/palette.hip) --------------------------------------------

@@ -26,7 +26,9 @@ The op-level networks of nnops.py (residual / Trans U-Nets) plan the same way: e
 (gradient fan-in through ``nnops.Fork``, filter layout and patch rearrangement kernels), ``optim.MultiAdam`` is plan-aware.
 Anything the recorder cannot own makes it refuse (``disabled`` says why) and the step runs eagerly: kernels launched by
 torch itself inside the step (a plug-in ``unet`` module, ``torch.cat`` of the pre-activation residual blocks, loss types
-other than "gan"), dropout masks drawn on the host side, per-launch profiling.
+other than "gan"), dropout masks drawn on the host side, per-launch profiling.  Dropout2d of the UnetWrapper families replays
+once the model has a device generator (``model.device_rng = DeviceRNG(seed)``): its launches read the step from the generator's
+device mirror, the recorded step ends with the ``pai_counter_add`` that advances it, and a replay moves only the host integer.
 """
 from __future__ import annotations
 
@@ -121,7 +123,7 @@ class _Recorder(TorchDispatchMode):
 
 
 class _Recorded:
-    __slots__ = ("items", "keep", "logs", "step0", "commits", "opt_steps", "static", "last_use")
+    __slots__ = ("items", "keep", "logs", "step0", "commits", "opt_steps", "static", "last_use", "rng_delta")
 
     def info(self):
         out = {"launches": 0, "waits": 0, "streams": 0, "runs": 0, "segments": 0, "host_nodes": 0}
@@ -172,11 +174,15 @@ class PlannedStep:
         for opt in m._all_optimizers():
             if not hasattr(opt, "plan_state"):
                 return f"{type(opt).__name__} is not a plan-aware optimizer"
+        # with a device generator on the model (UnetWrapper.device_rng) the Dropout2d sites are launches of the library that read
+        # the step from device memory: they replay.  Dropout of any other kind (the ViT's token and attention dropout) still
+        # draws from torch
+        rng = getattr(m, "device_rng", None)
         for mod in m.modules():
-            if isinstance(mod, torch.nn.Dropout2d) and mod.p > 0:
+            if isinstance(mod, torch.nn.Dropout2d) and mod.p > 0 and rng is None:
                 return "Dropout2d masks are drawn per step outside the C ABI"
             d = getattr(mod, "dropout", 0)
-            if isinstance(d, float) and d > 0:
+            if isinstance(d, float) and d > 0 and not (rng is not None and getattr(mod, "dropout_is_dropout2d", False)):
                 return "dropout > 0"
         return None
 
@@ -190,6 +196,12 @@ class PlannedStep:
         h = ops.handle_for(batch[0].device)
         sig.append(tuple(t.data_ptr() if t is not None else 0 for t in (h.workspace, h.scratch, h.wgrad_workspace)))
         sig.append(ops.is_deterministic())      # a plan replays the launches of the mode it was recorded in
+        rng = getattr(m, "device_rng", None)
+        if rng is not None:
+            # the recorded Dropout2d launches hold the seed and the rank by value and the ADDRESS of the step's device mirror.
+            # Asking for the mirror here, outside the plan, also rewrites a stale one (load_state_dict, an assignment to step)
+            # before the plan runs or is recorded; with the mirror in step it launches nothing
+            sig.append((rng.seed, rng.rank, rng.device_step(batch[0].device).data_ptr()))
         return tuple(sig)
 
     # ---- the call -------------------------------------------------------------------------------------------
@@ -236,6 +248,8 @@ class PlannedStep:
             s.copy_(b)
         rec.step0 = self._total_steps()
         before = m._pai_opt_steps
+        rng = getattr(m, "device_rng", None)
+        rng_before = rng.step if rng is not None else 0
         logs, orig_log = [], m.log
 
         def record_log(name, value, *a, **k):
@@ -259,6 +273,7 @@ class PlannedStep:
         rec.keep = recorder.keep
         rec.logs = logs
         rec.opt_steps = m._pai_opt_steps - before
+        rec.rng_delta = ((rng.step - rng_before) & 0xFFFFFFFF) if rng is not None else 0
         rec.commits = [opt.plan_commits() for opt in m._all_optimizers()]
         self.records += 1
         if recorder.foreign:
@@ -302,6 +317,9 @@ class PlannedStep:
         for opt, commits in zip(m._all_optimizers(), rec.commits):
             opt.plan_replayed(commits)
         m._pai_opt_steps += rec.opt_steps
+        rng = getattr(m, "device_rng", None)
+        if rng is not None and rec.rng_delta:
+            rng.replayed(rec.rng_delta)         # the plan held the counter add: the host integer follows, nothing is launched
         for name, value, a, k in rec.logs:
             m.log(name, value, *a, **k)
         self.replays += 1
